@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec of the batched ATACOM step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--env iiwa|planar|circle] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--env iiwa|planar|circle] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is ONE call of the hot path over one batch: `atacom_step` (C ABI, one HIP kernel launch) for
 B = 8192 IiwaAirHockey-7H environments per GPU -- action clip/scale, 4 x [constraint Jacobians + FK,
@@ -14,11 +14,24 @@ under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-ad
 torchrun by someone else it uses the ranks it was given (and refuses a WORLD_SIZE that contradicts --gpus).
 Each rank owns its own 8192-env shard (weak scaling, no collective on the data path).
 
-Timing: W warm-up steps, then BLOCKS of exactly K steps, each bracketed by barrier + synchronize on both sides,
-each block's time = MAX over ranks; blocks are repeated until >= --min-time seconds have been timed and the MEDIAN
-block is reported (a single 20-step block is 0.6 ms -- one scheduler hiccup would move the number by 10 %).
+Timing: short timed blocks for --warmup-seconds from a snapshot of the engine, which is then restored (a GPU fresh from
+set-up runs its first steps ~4 % slow, and a process's first timed block pays ~0.1 ms extra; the restore keeps the timed
+data independent of how many steps that took), W warm-up steps, then ONE block of exactly K steps, bracketed by
+barrier + synchronize on both sides, its time = MAX over ranks: `ms_per_step` = that time / K, `value` = all environments
+x K / that time.  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs (--dump-outputs), the
+JSON line.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+--dump-outputs DIR: after the timed block, what its LAST step returned to the caller -- obs [B, D], reward [B],
+absorbing [B] and last [B] (the flags as 0. / 1.) -- is written as DIR/<name>.npy in the engine's float type (rank 0's
+shard).  Inputs (initial states, actions) come from seeded generators, so two runs with the same arguments step the
+same data.  Above 64 MB in all, the same seeded sample of environments is kept from every array and its row indices are
+written as DIR/sample_rows.npy.
+
+--full adds everything else the benchmark measures: after the headline block, further K-step blocks until >= --min-time
+seconds have been timed (`timing`: median, p99, max -- a single 20-step block is 0.6 ms, one scheduler hiccup moves it
+by 10 %), and the extra objects below.  --no-cpu-baseline / --no-secondary leave parts of it out.
+
+Prints ONE JSON line (rank 0).  Extra objects (--full):
   roofline      the BINDING roof of the step kernel: fp32 vector ALU (bound "valu_f32": algorithmic FLOPs per launch /
                 mean kernel time from HIP events on the launch stream; this workload sits at 130 FLOP/B, far right of
                 the ridge -- SURVEY.md section 8d); `traffic` = measured HBM bytes per launch
@@ -240,9 +253,14 @@ def make_env(name, B, dev, gen, lanes=0, dtype=None, **kw):
 
 
 # ------------------------------------------------------------------------------------------ the timed loop
-def time_steps(env, actions, K, W, min_time, sync_all, max_over_ranks, max_blocks=20000):
+def time_steps(env, actions, K, W, min_time, sync_all, max_over_ranks, max_blocks=20000, repeat=True, outputs=None,
+               warmup_s=0.0):
     """W warm-up steps, then blocks of exactly K atacom_step launches; returns (per-block seconds [max over ranks],
-    mean kernel ms from HIP events on the launch stream over all timed launches)."""
+    mean kernel ms from HIP events on the launch stream over all timed launches).  repeat=False: the first block alone.
+    outputs: a dict that receives host copies of what the first block's last step returned (obs, reward, absorbing, last),
+    taken before any further block runs.  warmup_s: before the W steps, run blocks of min(K, 100) steps for at least this
+    many seconds from a snapshot of the engine and restore it -- the device and this timing path reach their steady state,
+    and the W + K steps that follow step the same data however many steps that took."""
     import numpy as np
     import torch
     B, D = env.batch, env.obs_dim
@@ -256,17 +274,14 @@ def time_steps(env, actions, K, W, min_time, sync_all, max_over_ranks, max_block
     # the C ABI per step (BatchedAtacomEnv.bind_step; the circle step is bound by the host, not by its 4 us kernel)
     steppers = [env.bind_step(actions[i], obs, rew, ab, last) for i in range(n_pool)]
     it = 0
-    for _ in range(W):
-        steppers[it % n_pool]()
-        it += 1
 
-    def block():
+    def block(n=K):
         nonlocal it
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         sync_all()                                   # barrier + synchronize
         t0 = time.perf_counter()
         e0.record()
-        for _ in range(K):
+        for _ in range(n):
             steppers[it % n_pool]()
             it += 1
         e1.record()
@@ -275,14 +290,52 @@ def time_steps(env, actions, K, W, min_time, sync_all, max_over_ranks, max_block
         sync_all()                                   # barrier + synchronize on the far side too
         return dt, e0.elapsed_time(e1)
 
+    if warmup_s > 0:
+        # through block() itself: the first block of a process pays ~0.1 ms more than the later ones, whatever came before
+        image = env.snapshot()
+        t0 = time.perf_counter()
+        while max_over_ranks([time.perf_counter() - t0])[0] < warmup_s:      # every rank runs as many blocks
+            block(min(K, 100))
+        env.restore(image)
+        del image
+    it = 0
+    for _ in range(W):
+        steppers[it % n_pool]()
+        it += 1
+
     first = block()
+    if outputs is not None:
+        outputs.update(obs=obs.cpu().numpy(), reward=rew.cpu().numpy(),
+                       absorbing=ab.cpu().numpy().astype(np.float32), last=last.cpu().numpy().astype(np.float32))
     # every rank must run the same number of blocks: decide it from the first block's max-over-ranks time
     t_first = max_over_ranks([first[0]])[0]
-    n_blocks = int(min(max(3, min_time / max(t_first, 1e-9)), max_blocks))
+    n_blocks = int(min(max(3, min_time / max(t_first, 1e-9)), max_blocks)) if repeat else 1
     res = [first] + [block() for _ in range(n_blocks - 1)]
     secs = max_over_ranks([r[0] for r in res])
     kern_ms = float(np.mean([r[1] for r in res])) / K
     return secs, kern_ms
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array [B, ...]} as path/<name>.npy in float32 / float64 (other types become float32).  Above
+    DUMP_LIMIT_BYTES in all, the same seeded sample of rows (environments) is kept from every array and the row indices
+    are written as sample_rows.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {n: np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float32))
+              for n, a in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    per_row = sum(a.nbytes for a in arrays.values()) / rows
+    if rows * per_row > DUMP_LIMIT_BYTES:
+        keep = int(DUMP_LIMIT_BYTES // (per_row + 8))
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {n: a[idx] for n, a in arrays.items()}
+        arrays['sample_rows'] = idx.astype(np.float64)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + '.npy'), a)
 
 
 def graphed_step_us(env, actions, n=20, reps=30):
@@ -352,15 +405,23 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=1000)
     ap.add_argument('--warmup', type=int, default=100)
+    ap.add_argument('--warmup-seconds', type=float, default=1.0,
+                    help='before the --warmup steps, step for this long from a snapshot that is then restored: the device '
+                         'reaches its steady state and the timed steps still see the same data on every run')
     ap.add_argument('--env', default='iiwa')
     ap.add_argument('--batch', type=int, default=8192)
     ap.add_argument('--lanes', type=int, default=0, help='kernel mapping: 0 = library policy, else lanes per env')
     ap.add_argument('--chart-mode', default='reference', choices=['reference', 'canonical'],
                     help="chart of the HEADLINE engine (default: the reference's; 'canonical' is the opt-in mode, also "
-                         "timed as a secondary record of the default run)")
-    ap.add_argument('--min-time', type=float, default=2.0, help='keep timing K-step blocks until this many seconds')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true')
+                         "timed as a secondary record of a --full run)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the timed block's last step returned as DIR/<name>.npy (rank 0's shard)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: repeated blocks, collection, rooflines, secondary '
+                         'and saturation records, CPU baseline')
+    ap.add_argument('--min-time', type=float, default=2.0, help='--full: keep timing K-step blocks until this many seconds')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='--full: leave out the secondary and saturation records')
     ap.add_argument('--cpu-seconds', type=float, default=4.0, help='budget of each scalar CPU-baseline leg')
     args = ap.parse_args()
 
@@ -387,8 +448,6 @@ def main():
     import numpy as np
     import torch
     import torch.distributed as dist
-    from rl_on_manifold_amd import MlpPolicy
-    from rl_on_manifold_amd.rollout import RolloutCollector
 
     # BENCH_DIST_BACKEND=gloo lets the multi-rank control flow be exercised on a box with fewer GPUs than ranks
     # (ranks then share devices); the driver's runs use the default, nccl (= RCCL), one rank per GPU.
@@ -423,17 +482,83 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
     env, init, rejected = make_env(args.env, B, dev, gen, args.lanes, chart_mode=args.chart_mode)
-    k, D = env.dims['null'], env.obs_dim
+    k = env.dims['null']
     n_pool = 64
     actions = torch.rand((n_pool, B, k), device=dev, generator=gen) * 2 - 1
 
-    # ---- headline: blocks of exactly K steps
-    secs, kern_ms = time_steps(env, actions, K, W, args.min_time, sync_all, max_over_ranks)
-    elapsed = float(np.median(secs))
-    c_avg, c_max, c_dq_max = env.get_constraints_logs()
-    if world > 1:
-        c_max, c_dq_max = max_over_ranks([c_max, c_dq_max])
+    # ---- headline: ONE block of exactly K steps
+    outs = {} if args.dump_outputs and rank == 0 else None
+    secs, kern_ms = time_steps(env, actions, K, W, args.min_time, sync_all, max_over_ranks, repeat=args.full, outputs=outs,
+                               warmup_s=args.warmup_seconds)
+    elapsed = secs[0]
+    if outs is not None:
+        dump_outputs(args.dump_outputs, outs)
 
+    result = None
+    if rank == 0:
+        result = {
+            'metric': 'env-steps/sec', 'value': world * B * K / elapsed, 'unit': 'env-steps/s', 'n_gpus': world,
+            'steps': K, 'warmup': W, 'warmup_seconds': args.warmup_seconds, 'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'config': {'workload': WORKLOAD[args.env] + ', batch %d per GPU' % B,
+                       'batch_per_gpu': B, 'global_batch': B * world,
+                       'lanes_per_env_requested': int(env.cfg.lanes_per_env), 'lanes_per_env': env.lanes_per_env, 'rollout_lanes_per_env': env.rollout_lanes_per_env, 'substeps': int(env.cfg.substeps),
+                       'horizon': int(env.cfg.horizon), 'path': 'atacom_step (1 launch / step) via C ABI',
+                       'chart_mode': args.chart_mode,
+                       'init': 'q_init + N(0, 0.05^2), one correction step, rejected unless all g < 0 and |f| < 1e-3 '
+                               '(%.1f %% of draws rejected); puck uniform in the hit range' % (100 * rejected)
+                               if args.env != 'circle' else 'half fixed reset point, half random valid states',
+                       'parallelism': 'env-shard x%d, no data-path collective' % world},
+        }
+    if args.full:
+        c_avg, c_max, c_dq_max = env.get_constraints_logs()
+        if world > 1:
+            c_max, c_dq_max = max_over_ranks([c_max, c_dq_max])
+        collection, pol_rate = collection_records(env, args.env, world, backend, dev, gen, sync_all, max_over_ranks)
+        if rank == 0:
+            traffic = (measured_traffic(args.env, args.chart_mode, lanes=env.lanes_per_env)
+                       if B == {'circle': 4096}.get(args.env, 8192) else None)
+            roof, roof_hbm = roofline_objects(args.env, B, kern_ms, traffic, args.chart_mode)
+            med = float(np.median(secs))
+            result.update({
+                # spread of the K-step blocks next to the headline block (one block in ~3000 took 70 x the
+                # median -- a host hiccup, visible here instead of hidden by the median)
+                'block_ms_p99': float(np.percentile(secs, 99)) * 1e3, 'block_ms_max': max(secs) * 1e3,
+                'timing': {'blocks': len(secs), 'block_steps': K, 'block_ms_median': med * 1e3,
+                           'block_ms_min': min(secs) * 1e3, 'block_ms_p99': float(np.percentile(secs, 99)) * 1e3,
+                           'block_ms_max': max(secs) * 1e3, 'ms_per_step_median': med / K * 1e3,
+                           'timed_seconds_total': float(sum(secs)),
+                           'statistic': 'blocks of (max over ranks); the headline is the first block'},
+                'max_abs_c': c_max, 'c_avg': c_avg, 'c_dq_max': c_dq_max,
+                'collection': collection,
+                'policy_rollout_kernel_env_steps_per_s_per_gpu': pol_rate,
+                'roofline': roof, 'roofline_hbm': roof_hbm,
+            })
+        # the engine of the headline run is no longer needed; secondary workloads and the CPU legs are N = 1 extras
+        if world == 1 and rank == 0:
+            if not args.no_secondary and args.env == 'iiwa' and args.batch == 8192:
+                result['secondary'] = secondary_records(dev, gen, K, W, sync_all, max_over_ranks)
+                result['saturation'] = saturation_records(dev, gen, K, W, sync_all, max_over_ranks)
+            if not args.no_cpu_baseline:
+                result['cpu_baseline'] = cpu_baseline(args.env, args.cpu_seconds, dev, init, k)
+    if rank == 0:
+        json_out.write(json.dumps(result) + '\n')
+        json_out.flush()
+    json_out.close()
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return result
+
+
+def collection_records(env, name, world, backend, dev, gen, sync_all, max_over_ranks):
+    """Config 5's collection phase on the headline engine: a 120-step rollout (one launch, packed records) + the one
+    all-gather, then the same collection with the actor MLP in the kernel.  Returns (collection dict, policy env-steps/s)."""
+    import numpy as np
+    import torch
+    from rl_on_manifold_amd import MlpPolicy
+    from rl_on_manifold_amd.rollout import RolloutCollector
+    B, k, D = env.batch, env.dims['null'], env.obs_dim
     # ---- collection phase of config 5: 120-step rollout (one launch, packed records) + the one all-gather
     T = 120
     col = RolloutCollector(env)
@@ -490,7 +615,7 @@ def main():
 
     # ---- the same collection with the actor MLP (18-64-64-5, random weights) + Gaussian noise inside the kernel (row N2)
     pol_rate = None
-    if args.env != 'circle':
+    if name != 'circle':
         gw = torch.Generator(device='cpu'); gw.manual_seed(0)
         Wts = [torch.randn(64, D, generator=gw) * 0.2, torch.zeros(64), torch.randn(64, 64, generator=gw) * 0.1,
                torch.zeros(64), torch.randn(k, 64, generator=gw) * 0.1, torch.zeros(k)]
@@ -505,52 +630,7 @@ def main():
         pol_rate = n_rep * T * B / (time.perf_counter() - t2)
     env.get_constraints_logs()
 
-    result = None
-    if rank == 0:
-        traffic = None
-        traffic = (measured_traffic(args.env, args.chart_mode, lanes=env.lanes_per_env)
-                   if B == {'circle': 4096}.get(args.env, 8192) else None)
-        roof, roof_hbm = roofline_objects(args.env, B, kern_ms, traffic, args.chart_mode)
-        result = {
-            'metric': 'env-steps/sec', 'value': world * B * K / elapsed, 'unit': 'env-steps/s', 'n_gpus': world,
-            'steps': K, 'warmup': W, 'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': WORKLOAD[args.env] + ', batch %d per GPU' % B,
-                       'batch_per_gpu': B, 'global_batch': B * world,
-                       'lanes_per_env_requested': int(env.cfg.lanes_per_env), 'lanes_per_env': env.lanes_per_env, 'rollout_lanes_per_env': env.rollout_lanes_per_env, 'substeps': int(env.cfg.substeps),
-                       'horizon': int(env.cfg.horizon), 'path': 'atacom_step (1 launch / step) via C ABI',
-                       'chart_mode': args.chart_mode,
-                       'init': 'q_init + N(0, 0.05^2), one correction step, rejected unless all g < 0 and |f| < 1e-3 '
-                               '(%.1f %% of draws rejected); puck uniform in the hit range' % (100 * rejected)
-                               if args.env != 'circle' else 'half fixed reset point, half random valid states',
-                       'parallelism': 'env-shard x%d, no data-path collective' % world},
-            # spread of the K-step blocks next to the median `ms_per_step` is computed from (one block in
-            # ~3000 took 70 x the median -- a host hiccup, visible here instead of hidden by the median)
-            'block_ms_p99': float(np.percentile(secs, 99)) * 1e3, 'block_ms_max': max(secs) * 1e3,
-            'timing': {'blocks': len(secs), 'block_steps': K, 'block_ms_median': elapsed * 1e3,
-                       'block_ms_min': min(secs) * 1e3, 'block_ms_p99': float(np.percentile(secs, 99)) * 1e3,
-                       'block_ms_max': max(secs) * 1e3,
-                       'timed_seconds_total': float(sum(secs)), 'statistic': 'median over blocks of (max over ranks)'},
-            'max_abs_c': c_max, 'c_avg': c_avg, 'c_dq_max': c_dq_max,
-            'collection': collection,
-            'policy_rollout_kernel_env_steps_per_s_per_gpu': pol_rate,
-            'roofline': roof, 'roofline_hbm': roof_hbm,
-        }
-    # the engine of the headline run is no longer needed; secondary workloads and the CPU legs are N = 1 extras
-    if world == 1 and rank == 0:
-        if not args.no_secondary and args.env == 'iiwa' and args.batch == 8192:
-            result['secondary'] = secondary_records(dev, gen, K, W, sync_all, max_over_ranks)
-            result['saturation'] = saturation_records(dev, gen, K, W, sync_all, max_over_ranks)
-        if not args.no_cpu_baseline:
-            result['cpu_baseline'] = cpu_baseline(args.env, args.cpu_seconds, dev, init, k)
-    if rank == 0:
-        json_out.write(json.dumps(result) + '\n')
-        json_out.flush()
-    json_out.close()
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return result
+    return collection, pol_rate
 
 
 def measured_traffic(name, chart='reference', dyn=False, lanes=0, tag=None):

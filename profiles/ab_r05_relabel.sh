@@ -12,7 +12,7 @@ done > $O/ab_microbench.log
 cat $O/ab_microbench.log
 for rep in 1 2; do
   for lib in build/ab/libatacom_r05base.so build/ab/libatacom_r05pre.so rl_on_manifold_amd/libatacom_hip.so; do
-    ATACOM_LIB=$lib python bench.py --steps 300 --warmup 30 --min-time 0.5 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', 'us/step', round(d['ms_per_step']*1e3, 3), 'kernel us', round(d['roofline']['kernel_ms']*1e3, 3), 'c_max', d['max_abs_c'])"
+    ATACOM_LIB=$lib python bench.py --full --steps 300 --warmup 30 --min-time 0.5 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$lib', 'us/step', round(d['ms_per_step']*1e3, 3), 'kernel us', round(d['roofline']['kernel_ms']*1e3, 3), 'c_max', d['max_abs_c'])"
   done
 done > $O/ab_bench.log
 cat $O/ab_bench.log

@@ -8,7 +8,7 @@ O=gpurun_out/prof_r02
 rm -rf $O; mkdir -p $O
 # 1. kernel trace + stats of the headline bench command (quad mapping, 8192 envs)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- \
-    python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.log 2>&1
+    python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.log 2>&1
 # 2. SQ counters, lanes 4 and 8 at 8192 envs (and the clock: GRBM_GUI_ACTIVE)
 for L in 4 8; do
   rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU \
@@ -25,8 +25,8 @@ MB_DYN=rigid_body MB_LANES=4,1 MB_BATCHES=8192,65536 python profiles/tools/gpu_m
 python profiles/tools/gpu_sens_probe.py 4 2048 40 2>&1 | grep -v amdgpu.ids > $O/sens_l4.log
 python profiles/tools/gpu_sens_probe.py 8 2048 40 2>&1 | grep -v amdgpu.ids > $O/sens_l8.log
 # 6. the bench lines: default, the driver's command, two ranks sharing the GPU over gloo
-python bench.py 2>/dev/null | tail -1 > $O/bench_default.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json
 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_cmd.json
-BENCH_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 200 --warmup 20 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $O/bench_gloo2.json
+BENCH_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 200 --warmup 20 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $O/bench_gloo2.json
 ls -R $O | head -50
 cut -c1-400 $O/bench_driver_cmd.json

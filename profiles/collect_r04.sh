@@ -12,15 +12,15 @@ python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | t
 tail -2 $O/gpu_suite.log; tail -1 $O/smoke.log
 # 1. kernel trace + stats of the headline bench command, the canonical-chart headline, configs 2 and 3, the rigid-body mode
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- \
-    python bench.py --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.log 2>&1
+    python bench.py --full --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_canonical -o s -- \
-    python bench.py --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary --chart-mode canonical > $O/bench_canonical_under_rocprof.log 2>&1
+    python bench.py --full --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary --chart-mode canonical > $O/bench_canonical_under_rocprof.log 2>&1
 python profiles/tools/trace_percentiles.py $O/stats "k_step<float, atacom::Iiwa, 4" > $O/launch_percentiles.log
 python profiles/tools/trace_percentiles.py $O/stats_canonical "k_step<float, atacom::Iiwa, 8" >> $O/launch_percentiles.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_planar -o s -- \
-    python bench.py --env planar --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_planar_under_rocprof.log 2>&1
+    python bench.py --full --env planar --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_planar_under_rocprof.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_circle -o s -- \
-    python bench.py --env circle --batch 4096 --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_circle_under_rocprof.log 2>&1
+    python bench.py --full --env circle --batch 4096 --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_circle_under_rocprof.log 2>&1
 MB_DYN=rigid_body_ff MB_WARM=60 MB_LANES=4 MB_BATCHES=8192 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_dyn -o s -- \
     python profiles/tools/gpu_microbench.py iiwa > $O/dyn_under_rocprof.log 2>&1
 # 2. HBM traffic of the step kernel, separate FETCH / WRITE passes, per workload
@@ -59,7 +59,7 @@ for l in 4 8; do MB_CHART=canonical python profiles/tools/gpu_sens_probe.py $l 8
 MB_CHART=canonical MB_DTYPE=f64 python profiles/tools/gpu_sens_probe.py 8 8192 40 2>&1 | grep -v amdgpu.ids > $O/soak_canonical_f64_l8.log
 python profiles/tools/gpu_sens_probe.py 4 8192 40 2>&1 | grep -v amdgpu.ids > $O/sens_soak_reference_l4.log
 # 8. the bench lines: default, the driver's command
-python bench.py 2>/dev/null | tail -1 > $O/bench_default.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json
 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_cmd.json
 find $O -name '*kernel_trace.csv' -size +2M -delete; find $O -name '*.db' -delete; find $O -name '*agent_info*' -delete
 du -sh $O

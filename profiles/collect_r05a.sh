@@ -12,7 +12,7 @@ MB_DTYPE=f64 MB_WARM=30 MB_ROLLOUT=1 MB_LANES=1,2,4,8 MB_BATCHES=8192 python pro
 cat $O/f64_lanes.log
 MB_WARM=30 MB_ROLLOUT=1 MB_LANES=4,8,4,8 MB_BATCHES=8192 python profiles/tools/gpu_microbench.py planar 2>&1 | grep -v amdgpu.ids > $O/planar_lanes.log
 cat $O/planar_lanes.log
-python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json
 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_cmd.json
 cut -c1-300 $O/bench_driver_cmd.json
 python - <<'PY'

@@ -9,13 +9,13 @@ TAG=${1:-r06}
 O=gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- \
-    python bench.py --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.log 2>&1
+    python bench.py --full --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.log 2>&1
 python profiles/tools/trace_percentiles.py $O/stats "k_step<float, atacom::Iiwa, 8" > $O/launch_percentiles.log
 cat $O/launch_percentiles.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_planar -o s -- \
-    python bench.py --env planar --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_planar_under_rocprof.log 2>&1
+    python bench.py --full --env planar --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_planar_under_rocprof.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_circle -o s -- \
-    python bench.py --env circle --batch 4096 --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_circle_under_rocprof.log 2>&1
+    python bench.py --full --env circle --batch 4096 --steps 300 --warmup 30 --min-time 0.3 --no-cpu-baseline --no-secondary > $O/bench_circle_under_rocprof.log 2>&1
 MB_DTYPE=f64 MB_WARM=60 MB_LANES=0 MB_BATCHES=8192 MB_ROLLOUT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_f64 -o s -- \
     python profiles/tools/gpu_microbench.py iiwa > $O/f64_under_rocprof.log 2>&1
 MB_WARM=60 MB_LANES=0 MB_BATCHES=65536 MB_ROLLOUT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_sat -o s -- \
@@ -31,7 +31,7 @@ done
 MB_WARM=60 MB_ROLLOUT=1 MB_LANES=0 MB_BATCHES=4096,8192,16384,65536,262144 python profiles/tools/gpu_microbench.py iiwa planar 2>&1 | grep -v amdgpu.ids > $O/lanes_vs_batch_reference.log
 MB_DTYPE=f64 MB_WARM=60 MB_ROLLOUT=1 MB_LANES=0 MB_BATCHES=4096,8192,16384,65536 python profiles/tools/gpu_microbench.py iiwa planar 2>&1 | grep -v amdgpu.ids > $O/lanes_vs_batch_f64.log
 cat $O/lanes_vs_batch_reference.log $O/lanes_vs_batch_f64.log
-( time python bench.py 2>/dev/null | tail -1 > $O/bench_default.json ) 2> $O/bench_default.time
+( time python bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json ) 2> $O/bench_default.time
 ( time python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_cmd.json ) 2> $O/bench_driver_cmd.time
 cat $O/bench_driver_cmd.time
 find $O -name '*kernel_trace.csv' -size +2M -delete; find $O -name '*.db' -delete; find $O -name '*agent_info*' -delete

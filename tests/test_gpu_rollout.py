@@ -375,11 +375,11 @@ def test_calls_leave_the_current_device_alone():
     assert torch.cuda.current_device() == 0
 
 
-def _run_bench(extra, env=None):
+def _run_bench(extra, env=None, full=True):
     e = dict(os.environ)
     e.update(env or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5',
-                        '--min-time', '0.1', '--no-cpu-baseline', '--no-secondary'] + extra,
+    opts = ['--full', '--min-time', '0.1', '--no-cpu-baseline', '--no-secondary'] if full else []
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '20', '--warmup', '5'] + opts + extra,
                        capture_output=True, text=True, timeout=600, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     # the contract: stdout is ONE line, the JSON (RCCL's version banner, printed through C stdio at process exit, used to
@@ -398,6 +398,28 @@ def test_bench_line_single_gpu():
     assert res['roofline']['bound'] == 'valu_f32' and abs(res['roofline']['frac'] - res['roofline']['achieved'] / 157.3) < 1e-12
     assert abs(res['roofline_hbm']['frac'] - res['roofline_hbm']['achieved'] / 8000.0) < 1e-12
     assert res['collection']['rccl_world1_selfgather']['identical'] is True
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries the headline alone; --dump-outputs writes what the
+    last timed step returned, and two runs with the same arguments step the same inputs to the same outputs."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ('run%d' % i)
+        res = _run_bench(['--gpus', '1', '--batch', '1024', '--dump-outputs', str(d)], full=False)
+        assert res['metric'] == 'env-steps/sec' and res['unit'] == 'env-steps/s' and res['higher_is_better'] is True
+        assert res['steps'] == 20 and res['warmup'] == 5 and res['dtype'] == 'f32' and res['n_gpus'] == 1
+        assert res['ms_per_step'] > 0 and abs(res['value'] - 1024 * 20 / (res['ms_per_step'] * 20e-3)) < 1e-6 * res['value']
+        for extra in ('timing', 'collection', 'roofline', 'secondary', 'saturation', 'cpu_baseline', 'max_abs_c'):
+            assert extra not in res
+        out = {n: np.load(str(d / (n + '.npy'))) for n in ('obs', 'reward', 'absorbing', 'last')}
+        assert sorted(os.listdir(str(d))) == ['absorbing.npy', 'last.npy', 'obs.npy', 'reward.npy']
+        assert out['obs'].shape == (1024, 18) and out['reward'].shape == out['absorbing'].shape == out['last'].shape == (1024,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+        assert set(np.unique(out['absorbing'])) <= {0.0, 1.0} and set(np.unique(out['last'])) <= {0.0, 1.0}
+        dumps.append(out)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
 
 
 def test_bench_spawns_its_own_ranks():

@@ -77,3 +77,33 @@ def test_bench_helpers():
     assert rc['algorithmic_flops_per_launch'] < rv['algorithmic_flops_per_launch'] / 3
     port = bench._free_port()
     assert 1024 < port < 65536
+
+
+def test_bench_dump_outputs_types_and_cap(tmp_path, monkeypatch):
+    """--dump-outputs: float arrays keep their type, flags become float32; above the cap every array keeps the same seeded
+    rows, listed in sample_rows.npy, and the files stay within the cap."""
+    import bench
+    B = 1000
+    rng = np.random.default_rng(3)
+    arrays = {'obs': rng.normal(size=(B, 18)).astype(np.float32), 'reward': rng.normal(size=B),
+              'absorbing': (rng.random(B) < 0.5).astype(np.uint8)}
+    bench.dump_outputs(str(tmp_path / 'all'), arrays)
+    got = {n: np.load(str(tmp_path / 'all' / (n + '.npy'))) for n in arrays}
+    assert got['obs'].dtype == np.float32 and got['reward'].dtype == np.float64 and got['absorbing'].dtype == np.float32
+    assert all(np.array_equal(got[n], arrays[n]) for n in arrays)
+    assert not (tmp_path / 'all' / 'sample_rows.npy').exists()
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 20000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == ['absorbing.npy', 'obs.npy', 'reward.npy', 'sample_rows.npy']
+    rows = np.load(str(tmp_path / 'a' / 'sample_rows.npy'))
+    assert rows.dtype == np.float64 and 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+    payload = 0
+    for n in files:
+        a, b = np.load(str(tmp_path / 'a' / n)), np.load(str(tmp_path / 'b' / n))
+        assert np.array_equal(a, b) and len(a) == len(rows)
+        payload += a.nbytes
+        if n != 'sample_rows.npy':
+            assert np.array_equal(a, arrays[n[:-4]][rows.astype(np.int64)].astype(a.dtype))
+    assert payload <= 20000
