@@ -237,6 +237,26 @@ int atacom_rollout_mlp(atacom_handle* h, int32_t n_steps, const atacom_mlp* net,
 int atacom_rollout_packed(atacom_handle* h, int32_t n_steps, const void* d_actions, const atacom_mlp* net,
                           const void* d_noise, void* d_records, int32_t record_batch_stride, void* stream);
 
+/* The same rollouts in the COMPACT record format, which does not repeat next_obs: the observation after step t is the record
+ * of step t + 1's obs, except where an auto-reset came between.  With T = n_steps, Bm = record_batch_stride and
+ * Fc = obs_dim + n_null + 3 (atacom_dims has no field for it):
+ *   d_records [T + 1, Bm, Fc]: rows 0..T-1 hold [obs | action | reward | absorbing | last] (the full record minus next_obs);
+ *     row T is the tail [obs after step T-1 (before that step's auto-reset) | zeros].  Rows batch..Bm-1 are not written.
+ *   d_ends [ends_capacity, obs_dim + 2]: one row [t, b, terminal obs] for every t < T-1 at which environment b of a handle
+ *     with cfg.auto_reset ended its episode (last = 1), so that obs[t + 1, b] is the reset observation.  t and b are exact
+ *     integers of the handle's float type.  Rows are appended through an atomic counter: their order is unspecified.
+ *   d_n_ends: a device int32, zeroed on `stream` at the start of the call, then the number of rows the call produced.  If it
+ *     exceeds ends_capacity the rows past the capacity were not written and the call's data is incomplete (the handle has
+ *     advanced all the same).  (T - 1) * batch rows always suffice.
+ * Reconstruction: next_obs[t] = obs[t + 1] for t < T - 1, next_obs[T - 1] = tail, then every d_ends row overwrites its
+ * (t, b) -- which gives the same result for any superset of the rows (a packer that lists every last = 1 row with t < T - 1).
+ * Validation and the supported policy variants are those of atacom_rollout_packed; n_steps and record_batch_stride must be
+ * < 2^24 and d_n_ends is required (d_ends may be NULL when ends_capacity is 0).  No host synchronisation: the call can be
+ * captured in a HIP graph (the counter reset is a hipMemsetAsync on `stream`). */
+int atacom_rollout_compact(atacom_handle* h, int32_t n_steps, const void* d_actions, const atacom_mlp* net,
+                           const void* d_noise, void* d_records, int32_t record_batch_stride, void* d_ends,
+                           int32_t ends_capacity, int32_t* d_n_ends, void* stream);
+
 /* get_constraints_logs (atacom.py:207-216; circle_base.py:109-115): out = {c_avg, c_max, c_dq_max} over every
  * (env, step) logged since the last clear.  Synchronises `stream`. */
 int atacom_get_stats(atacom_handle* h, double out[3], int32_t clear, void* stream);

@@ -18,7 +18,7 @@ def __getattr__(name):
                 'CircleEnvTerminated', 'VectorizedAtacomEnv'):
         from . import envs
         return getattr(envs, name)
-    if name in ('RolloutCollector', 'RecordLayout'):
+    if name in ('RolloutCollector', 'RecordLayout', 'CompactRecordLayout'):
         from . import rollout
         return getattr(rollout, name)
     raise AttributeError(name)

@@ -550,7 +550,7 @@ int atacom_rollout(atacom_handle* h, int32_t n_steps, const void* d_actions, voi
         return fail(ATACOM_E_INVALID, "atacom_rollout: all buffers except d_next_obs are required");
     ON_DEVICE(h);
     stepper(h).rollout(h->cfg, rollout_lanes(h), n_steps, h->f, h->ip, d_actions, d_obs, d_next_obs, d_reward,
-                       d_absorbing, d_last, nullptr, 0, (hipStream_t)stream);
+                       d_absorbing, d_last, nullptr, 0, nullptr, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return ATACOM_OK;
 }
@@ -566,7 +566,7 @@ int atacom_rollout_mlp(atacom_handle* h, int32_t n_steps, const atacom_mlp* net,
         return fail(ATACOM_E_INVALID, "atacom_rollout_mlp: all output buffers except d_next_obs are required");
     ON_DEVICE(h);
     const int rc = stepper(h).rollout_mlp(h->cfg, policy_lanes(h), n_steps, *net, h->f, h->ip, d_noise, d_obs,
-                                       d_next_obs, d_actions, d_reward, d_absorbing, d_last, nullptr, 0,
+                                       d_next_obs, d_actions, d_reward, d_absorbing, d_last, nullptr, 0, nullptr,
                                        (hipStream_t)stream);
     if (rc != ATACOM_OK)
         return fail(ATACOM_E_UNSUPPORTED, "atacom_rollout_mlp: only planar / iiwa with hidden = 64 are compiled in (not: the canonical chart together with noise options / rigid-body mode; float64: reference chart, kinematic, no noise options)");
@@ -574,30 +574,58 @@ int atacom_rollout_mlp(atacom_handle* h, int32_t n_steps, const atacom_mlp* net,
     return ATACOM_OK;
 }
 
-int atacom_rollout_packed(atacom_handle* h, int32_t n_steps, const void* d_actions, const atacom_mlp* net,
-                          const void* d_noise, void* d_records, int32_t record_batch_stride, void* stream) {
-    if (!h) return fail(ATACOM_E_INVALID, "atacom_rollout_packed: null handle");
-    if (n_steps <= 0) return fail(ATACOM_E_INVALID, "atacom_rollout_packed: n_steps must be positive");
-    if (!d_records) return fail(ATACOM_E_INVALID, "atacom_rollout_packed: d_records is required");
+// atacom_rollout_packed and atacom_rollout_compact: one validation, one dispatch; cx selects the compact format
+static int rollout_records(atacom_handle* h, const char* fn, int32_t n_steps, const void* d_actions, const atacom_mlp* net,
+                           const void* d_noise, void* d_records, int32_t record_batch_stride, const atacom::CompactArgs* cx,
+                           void* stream) {
+    const std::string name(fn);
+    if (!h) return fail(ATACOM_E_INVALID, name + ": null handle");
+    if (n_steps <= 0) return fail(ATACOM_E_INVALID, name + ": n_steps must be positive");
+    if (!d_records) return fail(ATACOM_E_INVALID, name + ": d_records is required");
     if ((d_actions != nullptr) == (net != nullptr))
-        return fail(ATACOM_E_INVALID, "atacom_rollout_packed: give either d_actions or a policy network");
+        return fail(ATACOM_E_INVALID, name + ": give either d_actions or a policy network");
     if (record_batch_stride < h->cfg.batch)
-        return fail(ATACOM_E_INVALID, "atacom_rollout_packed: record_batch_stride must be >= batch");
+        return fail(ATACOM_E_INVALID, name + ": record_batch_stride must be >= batch");
+    if (cx) {
+        // (t, b) of an exception row are stored in the handle's float type: exact integers below 2^24 in float32
+        if (n_steps >= (1 << 24) || record_batch_stride >= (1 << 24))
+            return fail(ATACOM_E_INVALID, name + ": n_steps and record_batch_stride must be < 2^24");
+        if (!cx->count) return fail(ATACOM_E_INVALID, name + ": d_n_ends is required");
+        if (cx->cap < 0 || (cx->cap > 0 && !cx->ends))
+            return fail(ATACOM_E_INVALID, name + ": ends_capacity must be >= 0, and d_ends given when it is positive");
+    }
+    if (net) {
+        const int vrc = check_mlp(h, net, fn);
+        if (vrc != ATACOM_OK) return vrc;
+    }
     ON_DEVICE(h);
+    if (cx) HIP_TRY(hipMemsetAsync(cx->count, 0, sizeof(int32_t), (hipStream_t)stream));
     if (d_actions) {
         stepper(h).rollout(h->cfg, rollout_lanes(h), n_steps, h->f, h->ip, d_actions, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, d_records, record_batch_stride, (hipStream_t)stream);
+                           nullptr, nullptr, d_records, record_batch_stride, cx, (hipStream_t)stream);
     } else {
-        const int vrc = check_mlp(h, net, "atacom_rollout_packed");
-        if (vrc != ATACOM_OK) return vrc;
         const int rc = stepper(h).rollout_mlp(h->cfg, policy_lanes(h), n_steps, *net, h->f, h->ip, d_noise, nullptr,
-                                              nullptr, nullptr, nullptr, nullptr, nullptr, d_records, record_batch_stride,
+                                              nullptr, nullptr, nullptr, nullptr, nullptr, d_records, record_batch_stride, cx,
                                               (hipStream_t)stream);
         if (rc != ATACOM_OK)
-            return fail(ATACOM_E_UNSUPPORTED, "atacom_rollout_packed: only planar / iiwa with hidden = 64 are compiled in (not: the canonical chart together with noise options / rigid-body mode; float64: reference chart, kinematic, no noise options)");
+            return fail(ATACOM_E_UNSUPPORTED, name + ": only planar / iiwa with hidden = 64 are compiled in (not: the canonical chart together with noise options / rigid-body mode; float64: reference chart, kinematic, no noise options)");
     }
     HIP_TRY(hipGetLastError());
     return ATACOM_OK;
+}
+
+int atacom_rollout_packed(atacom_handle* h, int32_t n_steps, const void* d_actions, const atacom_mlp* net,
+                          const void* d_noise, void* d_records, int32_t record_batch_stride, void* stream) {
+    return rollout_records(h, "atacom_rollout_packed", n_steps, d_actions, net, d_noise, d_records, record_batch_stride,
+                           nullptr, stream);
+}
+
+int atacom_rollout_compact(atacom_handle* h, int32_t n_steps, const void* d_actions, const atacom_mlp* net,
+                           const void* d_noise, void* d_records, int32_t record_batch_stride, void* d_ends,
+                           int32_t ends_capacity, int32_t* d_n_ends, void* stream) {
+    const atacom::CompactArgs cx{d_ends, d_n_ends, ends_capacity};
+    return rollout_records(h, "atacom_rollout_compact", n_steps, d_actions, net, d_noise, d_records, record_batch_stride,
+                           &cx, stream);
 }
 
 int atacom_set_seed(atacom_handle* h, int32_t seed) {

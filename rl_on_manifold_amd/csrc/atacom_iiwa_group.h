@@ -10,10 +10,11 @@
     X __global__ void k_step<float, Iiwa, L, H, false, 0, false>(const Params<float>, float*, int*, const float*, float*,     \
                                                                  float*, uint8_t*, uint8_t*, const uint8_t*);                  \
     X __global__ void k_rollout<float, Iiwa, L, H, false, 0, false>(const Params<float>, int, float*, int*, const float*,     \
-                                                                    float*, float*, float*, uint8_t*, uint8_t*, float*, int);  \
+                                                                    float*, float*, float*, uint8_t*, uint8_t*, float*, int,   \
+                                                                    const CompactEnds<float>);                                 \
     X __global__ void k_rollout_mlp<float, Iiwa, L, H, 64, false, 0, false>(                                                   \
         const Params<float>, const MlpArgs<float>, int, float*, int*, const float*, float*, float*, float*, float*, uint8_t*,  \
-        uint8_t*, float*, int);
+        uint8_t*, float*, int, const CompactEnds<float>);
 #define ATACOM_IIWA_GROUP_KERNELS(X)                                                                                           \
     ATACOM_IIWA_GROUP_KERNELS_OF(X, 8, true) ATACOM_IIWA_GROUP_KERNELS_OF(X, 8, false)                                         \
     ATACOM_IIWA_GROUP_KERNELS_OF(X, 4, true) ATACOM_IIWA_GROUP_KERNELS_OF(X, 4, false)

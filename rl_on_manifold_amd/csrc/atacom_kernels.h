@@ -86,6 +86,50 @@ struct Record {
     static constexpr int OBS = 0, ACT = E::OBS, REW = ACT + E::NK, NOBS = REW + 1, ABS = NOBS + E::OBS, LAST = ABS + 1,
                          F = LAST + 1;
 };
+// The compact record (atacom_rollout_compact): the same fields without next_obs, which repeats the next step's obs except
+// where an auto-reset came between.  Rows 0..T-1 are records, row T the tail [obs after step T-1 | zeros]; every episode end
+// at t < T-1 of an auto-resetting handle appends one row [t, b, terminal obs] of END floats to a separate list.
+template <typename E>
+struct RecordCompact {
+    static constexpr int OBS = 0, ACT = E::OBS, REW = ACT + E::NK, ABS = REW + 1, LAST = ABS + 1, F = LAST + 1,
+                         END = E::OBS + 2;
+};
+static_assert(Record<Iiwa>::ABS == Record<Iiwa>::F - 2 && RecordCompact<Iiwa>::ABS == RecordCompact<Iiwa>::F - 2,
+              "absorbing and last close both record formats");
+// Where the compact mode's exceptions go: `count` (device int, zeroed by the host before the launch) is the append cursor;
+// rows at an index >= cap are counted but not written.  count == nullptr: the full record format.
+template <typename T>
+struct CompactEnds {
+    T* ends;
+    int* count;
+    int cap;
+};
+
+// Compact format: the destination of the observation after step t of environment b -- the tail row (last step; its trailing
+// fields are zeroed here), an appended exception row (an episode end of an auto-resetting handle before the last step) or
+// nowhere.  Called by the committing thread only.  (Every address is derived from the step's record pointer or the appended
+// index: a per-environment constant such as the tail's address would be hoisted out of the step loop and held in registers
+// across the solver.)
+template <typename T, typename E>
+__device__ __forceinline__ T* compact_next_obs_slot(const CompactEnds<T>& cx, T* rrow, int rec_ld, int n_steps, int t, int b,
+                                                    bool reset_next) {
+    using RC = RecordCompact<E>;
+    if (t == n_steps - 1) {
+        T* const tail = rrow + (size_t)rec_ld * RC::F;          // row T: the row after the last step's
+#pragma unroll
+        for (int i = E::OBS; i < RC::F; ++i) tail[i] = T(0);
+        return tail;
+    }
+    if (!reset_next) return nullptr;
+    const int i = atomicAdd(cx.count, 1);
+    if (i >= cx.cap) return nullptr;
+    int bv = b;
+    asm volatile("" : "+v"(bv));        // converted here, not hoisted out of the step loop into a register held across it
+    T* const e = cx.ends + (size_t)i * RC::END;
+    e[0] = T(t);
+    e[1] = T(bv);
+    return e + 2;
+}
 
 template <typename T, typename E>
 struct EnvState {
@@ -1238,10 +1282,12 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_rollout(const Params<T> P, int
                                                   int* __restrict__ ip, const T* __restrict__ actions,
                                                   T* __restrict__ obs, T* __restrict__ next_obs,
                                                   T* __restrict__ reward, uint8_t* __restrict__ absorbing,
-                                                  uint8_t* __restrict__ last, T* __restrict__ rec, int rec_ld) {
+                                                  uint8_t* __restrict__ last, T* __restrict__ rec, int rec_ld,
+                                                  const CompactEnds<T> cx) {
     using L = Planes<E>;
     using R = Record<E>;
     const int B = P.batch;
+    const int rf = cx.count ? RecordCompact<E>::F : R::F;          // floats per record: compact or full format
     const int gt = blockIdx.x * BLOCK<LANES> + threadIdx.x;
     const int b = gt / LANES;
     const int lq = gt % LANES;
@@ -1259,7 +1305,7 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_rollout(const Params<T> P, int
 #pragma unroll 1
     for (int t = 0; t < n_steps; ++t) {
         const size_t row = (size_t)t * B + b;
-        T* const rrow = rec ? rec + ((size_t)t * rec_ld + b) * R::F : nullptr;     // packed record of (t, b)
+        T* const rrow = rec ? rec + ((size_t)t * rec_ld + b) * rf : nullptr;       // packed record of (t, b)
         T act[E::NK];
 #pragma unroll
         for (int k = 0; k < E::NK; ++k) act[k] = act_next[k];
@@ -1281,10 +1327,15 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_rollout(const Params<T> P, int
         env_step<T, E, LANES, HOLD, DYN, true, CHART>(P, st, act, out, lq, ref);
         if (lq == 0) {
             if (rec) {
-                write_obs<T, E>(P, st, rrow + R::NOBS, ref);
+                if (!cx.count) {
+                    write_obs<T, E>(P, st, rrow + R::NOBS, ref);
+                } else {
+                    T* const nd = compact_next_obs_slot<T, E>(cx, rrow, rec_ld, n_steps, t, b, P.auto_reset && out.last);
+                    if (nd) write_obs<T, E>(P, st, nd, ref);
+                }
                 rrow[R::REW] = out.reward;
-                rrow[R::ABS] = out.absorbing ? T(1) : T(0);
-                rrow[R::LAST] = out.last ? T(1) : T(0);
+                rrow[rf - 2] = out.absorbing ? T(1) : T(0);          // absorbing, last: the record's two final fields
+                rrow[rf - 1] = out.last ? T(1) : T(0);
             } else {
                 if (next_obs) write_obs<T, E>(P, st, next_obs + row * E::OBS, ref);
                 reward[row] = out.reward;
@@ -1340,9 +1391,11 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
                                                       const T* __restrict__ noise, T* __restrict__ obs,
                                                       T* __restrict__ next_obs, T* __restrict__ actions_out,
                                                       T* __restrict__ reward, uint8_t* __restrict__ absorbing,
-                                                      uint8_t* __restrict__ last, T* __restrict__ rec, int rec_ld) {
+                                                      uint8_t* __restrict__ last, T* __restrict__ rec, int rec_ld,
+                                                      const CompactEnds<T> cx) {
     using L = Planes<E>;
     using R = Record<E>;
+    const int rf = cx.count ? RecordCompact<E>::F : R::F;          // floats per record: compact or full format
     constexpr bool MFMA = MlpPath<T, E, LANES, H>::MFMA;
     static_assert(LANES <= 4 || MFMA || (ATACOM_MLP8_VALU && std::is_same<T, float>::value), "8 lanes per environment: float32 only");
     constexpr int THREADS = MlpPath<T, E, LANES, H>::THREADS;
@@ -1406,7 +1459,7 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
             act[k] = num<T>::fma(sig[k], eps[k], act[k]);
             if (net.squash) act[k] = num<T>::tanh(act[k]);
         }
-        T* const rrow = rec ? rec + ((size_t)t * rec_ld + b) * R::F : nullptr;
+        T* const rrow = rec ? rec + ((size_t)t * rec_ld + b) * rf : nullptr;
         if (lq == 0 && valid) {
             T* const od = rec ? rrow + R::OBS : obs + row * E::OBS;
             T* const ad = rec ? rrow + R::ACT : actions_out + row * E::NK;
@@ -1423,12 +1476,17 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
 #define ATACOM_MLP_PARK 1           // -DATACOM_MLP_PARK=0: the build that shows the defect described at env_step (PARKDYN)
 #endif
         env_step<T, E, LANES, HOLD, DYN, (LANES > 1), CHART, THREADS, /*PARKDYN*/ DYN && ATACOM_MLP_PARK>(P, st, act, out, lq, ref);
-        if (lq == 0 && valid) {
+        if (lq == 0 && valid) {           // (shadow lanes of the MFMA path never append an exception row or write a tail)
             if (rec) {
-                write_obs<T, E>(P, st, rrow + R::NOBS, ref);
+                if (!cx.count) {
+                    write_obs<T, E>(P, st, rrow + R::NOBS, ref);
+                } else {
+                    T* const nd = compact_next_obs_slot<T, E>(cx, rrow, rec_ld, n_steps, t, b, P.auto_reset && out.last);
+                    if (nd) write_obs<T, E>(P, st, nd, ref);
+                }
                 rrow[R::REW] = out.reward;
-                rrow[R::ABS] = out.absorbing ? T(1) : T(0);
-                rrow[R::LAST] = out.last ? T(1) : T(0);
+                rrow[rf - 2] = out.absorbing ? T(1) : T(0);          // absorbing, last: the record's two final fields
+                rrow[rf - 1] = out.last ? T(1) : T(0);
             } else {
                 if (next_obs) write_obs<T, E>(P, st, next_obs + row * E::OBS, ref);
                 reward[row] = out.reward;

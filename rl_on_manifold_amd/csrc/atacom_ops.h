@@ -7,6 +7,13 @@
 
 namespace atacom {
 
+// The exception list of the compact record format (atacom_rollout_compact); a null pointer selects the full format
+struct CompactArgs {
+    void* ends;      // [cap, obs_dim + 2] of the handle's float type
+    int* count;      // device int32, zeroed on the stream before the launch
+    int cap;
+};
+
 struct EnvOps {
     int n_planes, n_iplanes;     // per-environment allocation: values in the float buffer (hot + cold groups of four), ints
     int state_dim, init_dim, obs_dim, nq, nf, ng, nk;
@@ -16,11 +23,12 @@ struct EnvOps {
     void (*step)(const atacom_config&, int lanes, void* f, int* ip, const void* act, void* obs, void* rew,
                  uint8_t* ab, uint8_t* last, const uint8_t* mask, hipStream_t s);
     void (*rollout)(const atacom_config&, int lanes, int n_steps, void* f, int* ip, const void* acts, void* obs,
-                    void* nobs, void* rew, uint8_t* ab, uint8_t* last, void* rec, int rec_ld, hipStream_t s);
+                    void* nobs, void* rew, uint8_t* ab, uint8_t* last, void* rec, int rec_ld, const CompactArgs* cx,
+                    hipStream_t s);
     // returns 0, or -3 if the (env, hidden size) combination is not compiled in
     int (*rollout_mlp)(const atacom_config&, int lanes, int n_steps, const atacom_mlp& net, void* f, int* ip,
                        const void* noise, void* obs, void* nobs, void* acts, void* rew, uint8_t* ab, uint8_t* last,
-                       void* rec, int rec_ld, hipStream_t s);
+                       void* rec, int rec_ld, const CompactArgs* cx, hipStream_t s);
     void (*reset)(const atacom_config&, void* f, int* ip, const uint8_t* mask, const void* init, void* obs,
                   hipStream_t s);
     void (*fill_init)(const atacom_config&, void* f, int* ip, const void* row, hipStream_t s);
@@ -43,10 +51,11 @@ struct VariantOps {
     void (*step)(const atacom_config&, int lanes, void* f, int* ip, const void* act, void* obs, void* rew,
                  uint8_t* ab, uint8_t* last, const uint8_t* mask, hipStream_t s);
     void (*rollout)(const atacom_config&, int lanes, int n_steps, void* f, int* ip, const void* acts, void* obs,
-                    void* nobs, void* rew, uint8_t* ab, uint8_t* last, void* rec, int rec_ld, hipStream_t s);
+                    void* nobs, void* rew, uint8_t* ab, uint8_t* last, void* rec, int rec_ld, const CompactArgs* cx,
+                    hipStream_t s);
     int (*rollout_mlp)(const atacom_config&, int lanes, int n_steps, const atacom_mlp& net, void* f, int* ip,
                        const void* noise, void* obs, void* nobs, void* acts, void* rew, uint8_t* ab, uint8_t* last,
-                       void* rec, int rec_ld, hipStream_t s);
+                       void* rec, int rec_ld, const CompactArgs* cx, hipStream_t s);
     // the canonical chart as a primitive: A [n, c, q], s [n, g], y [n, c], alpha [n, k] -> mu [n, q + g]
     void (*chart_mu)(int n, const void* A, const void* sl, const void* y, const void* alpha, double tol, void* mu,
                      hipStream_t s);

@@ -39,6 +39,11 @@ static Params<T> make_params(const atacom_config& c) {
 
 static inline int nblk(int n, int per) { return (n + per - 1) / per; }
 
+template <typename T>
+static CompactEnds<T> compact_ends(const CompactArgs* cx) {
+    return cx ? CompactEnds<T>{(T*)cx->ends, cx->count, cx->cap} : CompactEnds<T>{nullptr, nullptr, 0};
+}
+
 // ------------------------------------------------------------------ the census of lane mappings (round 6)
 // Which "lanes per environment" forms of the stepping kernels are INSTANTIATED for a (scalar type, environment, variant).
 // One rule, shared by the dispatchers below and -- through lanes_run in the launch tables -- by the C ABI, so that
@@ -102,19 +107,20 @@ struct Variant {
         });
     }
     static void rollout(const atacom_config& c, int lanes, int n_steps, void* f, int* ip, const void* acts, void* obs,
-                        void* nobs, void* rew, uint8_t* ab, uint8_t* last, void* rec, int rec_ld, hipStream_t s) {
+                        void* nobs, void* rew, uint8_t* ab, uint8_t* last, void* rec, int rec_ld, const CompactArgs* cx,
+                        hipStream_t s) {
         with_mapping<KIND_ROLLOUT>(lanes, c.hold_q != 0, [&](auto lc, auto hc) {
             constexpr int LANES = decltype(lc)::value;
             constexpr bool HOLD = decltype(hc)::value;
             hipLaunchKernelGGL((k_rollout<T, E, LANES, HOLD, DYN, CHART, NOISE>), dim3(nblk(c.batch * LANES, BLOCK<LANES>)),
                                dim3(BLOCK<LANES>), 0, s, make_params<T>(c), n_steps, (T*)f, ip, (const T*)acts, (T*)obs,
-                               (T*)nobs, (T*)rew, ab, last, (T*)rec, rec_ld);
+                               (T*)nobs, (T*)rew, ab, last, (T*)rec, rec_ld, compact_ends<T>(cx));
         });
     }
     template <int LANES, bool HOLD>
     static void launch_mlp(const atacom_config& c, int n_steps, const MlpArgs<T>& a, void* f, int* ip,
                            const void* noise, void* obs, void* nobs, void* acts, void* rew, uint8_t* ab,
-                           uint8_t* last, void* rec, int rec_ld, hipStream_t s) {
+                           uint8_t* last, void* rec, int rec_ld, const CompactArgs* cx, hipStream_t s) {
         constexpr int H = 64;
         size_t lds_floats = 2 * MlpLds<E::OBS, H, E::NK>::TOTAL;
         if constexpr (MlpPath<T, E, LANES, H>::MFMA) {
@@ -125,11 +131,11 @@ struct Variant {
         constexpr int THREADS = MlpPath<T, E, LANES, H>::THREADS;
         hipLaunchKernelGGL((k_rollout_mlp<T, E, LANES, HOLD, H, DYN, CHART, NOISE>), dim3(nblk(c.batch * LANES, THREADS)),
                            dim3(THREADS), lds_bytes, s, make_params<T>(c), a, n_steps, (T*)f, ip, (const T*)noise, (T*)obs,
-                           (T*)nobs, (T*)acts, (T*)rew, ab, last, (T*)rec, rec_ld);
+                           (T*)nobs, (T*)acts, (T*)rew, ab, last, (T*)rec, rec_ld, compact_ends<T>(cx));
     }
     static int rollout_mlp(const atacom_config& c, int lanes, int n_steps, const atacom_mlp& net, void* f, int* ip,
                            const void* noise, void* obs, void* nobs, void* acts, void* rew, uint8_t* ab, uint8_t* last,
-                           void* rec, int rec_ld, hipStream_t s) {
+                           void* rec, int rec_ld, const CompactArgs* cx, hipStream_t s) {
         if (E::ID == 0 || net.hidden != 64) return ATACOM_E_UNSUPPORTED;
         MlpArgs<T> a;
         a.W1 = (const T*)net.W1; a.b1 = (const T*)net.b1; a.W2 = (const T*)net.W2; a.b2 = (const T*)net.b2;
@@ -149,7 +155,7 @@ struct Variant {
             else
             with_mapping<KIND_MLP>(lanes, c.hold_q != 0, [&](auto lc, auto hc) {
                 launch_mlp<decltype(lc)::value, decltype(hc)::value>(c, n_steps, a, f, ip, noise, obs, nobs, acts, rew, ab,
-                                                                     last, rec, rec_ld, s);
+                                                                     last, rec, rec_ld, cx, s);
             });
         }
         return ATACOM_OK;

@@ -364,6 +364,58 @@ class BatchedAtacomEnv:
                                                         self._stream()))
         return out
 
+    def rollout_compact(self, actions=None, policy=None, n_steps=None, noise=None, out=None, batch_stride=None,
+                        ends_capacity=None):
+        """rollout_packed() in the compact record format (atacom_rollout_compact), which does not repeat next_obs.
+        Returns (records [T + 1, batch_stride, D + k + 3], ends [n, D + 2], n):
+          records rows 0..T-1 = [obs | action | reward | absorbing | last], row T = [obs after the last step | zeros];
+          ends = one row [t, b, terminal obs] per episode end at t < T-1 of an auto-resetting engine, in no particular order.
+        rollout.CompactRecordLayout rebuilds the full records' fields from them.  ends_capacity (default (T-1) * batch, the
+        worst case) rows are allocated on the device; only the n written ones are ever sent by a collector.  `out` =
+        (records, ends) caller buffers of those shapes (ends [ends_capacity, D + 2]); padding rows are zeroed as in
+        rollout_packed.  Reads the row count back: synchronises the current stream once.  Raises ValueError when the count
+        exceeds the capacity -- the rows past it are lost, and the engine has advanced all the same."""
+        B, k, D = self.batch, self.dims['null'], self.obs_dim
+        Fc = D + k + 3
+        if (actions is None) == (policy is None):
+            raise ValueError("give either actions or policy")
+        T = int(actions.shape[0]) if actions is not None else int(n_steps)
+        ld = B if batch_stride is None else int(batch_stride)
+        cap = max(T - 1, 0) * B if ends_capacity is None else int(ends_capacity)
+        if cap < 0:
+            raise ValueError("ends_capacity must be >= 0")
+        if out is None:
+            rec = (torch.empty if ld == B else torch.zeros)((T + 1, ld, Fc), device=self.device, dtype=self.dtype)
+            ends = torch.empty((cap, D + 2), device=self.device, dtype=self.dtype)
+        else:
+            rec, ends = out
+            if tuple(rec.shape) != (T + 1, ld, Fc) or not rec.is_contiguous() or rec.dtype != self.dtype \
+                    or not self._on_my_device(rec):
+                raise ValueError("out[0] must be a contiguous [%d, %d, %d] tensor of the engine's dtype on %s"
+                                 % (T + 1, ld, Fc, self.device))
+            if ends.dim() != 2 or ends.shape[0] < cap or ends.shape[1] != D + 2 or not ends.is_contiguous() \
+                    or ends.dtype != self.dtype or not self._on_my_device(ends):
+                raise ValueError("out[1] must be a contiguous [>= %d, %d] tensor of the engine's dtype on %s"
+                                 % (cap, D + 2, self.device))
+            if ld > B:
+                rec[:, B:].zero_()
+        n_ends = torch.empty((1,), device=self.device, dtype=torch.int32)
+        if actions is not None:
+            a = self._as_dev(actions, (T, B, k))
+            _lib.check(self._lib.atacom_rollout_compact(self._h, T, _ptr(a), None, None, _ptr(rec), ld,
+                                                         _ptr(ends) if cap > 0 else None, cap, _ptr(n_ends), self._stream()))
+        else:
+            net = policy.as_struct(self)
+            nz = None if noise is None else self._as_dev(noise, (T, B, k))
+            _lib.check(self._lib.atacom_rollout_compact(self._h, T, None, C.byref(net), _ptr(nz), _ptr(rec), ld,
+                                                         _ptr(ends) if cap > 0 else None, cap, _ptr(n_ends), self._stream()))
+        n = int(n_ends.item())
+        if n > cap:
+            raise ValueError("rollout_compact: %d episode-end rows, capacity %d -- the rows past the capacity were not written. "
+                             "The engine has advanced: take a snapshot() before the call to retry it with a larger "
+                             "ends_capacity" % (n, cap))
+        return rec, ends[:n], n
+
     def unpack_records(self, rec):
         """Views into packed records [..., record_dim] (no copy)."""
         D, k = self.obs_dim, self.dims['null']

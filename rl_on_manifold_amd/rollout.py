@@ -18,6 +18,15 @@ of the gathered buffer holds sizes[r] valid env rows followed by ZERO rows, so `
 contains those padding records -- `RecordLayout.valid_mask()` selects the real ones, `time_major()` drops them.  For config 5: 120 x 8192 x 44 floats = 173 MB sent per rank, 1.38 GB received; xGMI is
 point-to-point, so one large collective amortises the per-link setup far better than six small ones.
 Constraint statistics are reduced with one MAX and one SUM all-reduce of two numbers each.
+
+Compact format (RolloutCollector(record_format='compact'), opt-in): next_obs is the next record's obs except where an
+auto-reset came between, so the kernel (atacom_rollout_compact) writes records [T + 1, Bm, D + k + 3] -- the full record
+minus next_obs, plus a tail row holding the observation after the last step -- and appends one row [t, b, terminal obs] per
+episode end before the last step.  The gather is then ONE all-gather of the W exception counts (this reads the count back:
+one stream synchronisation per collection) and ONE all-gather of each rank's flat segment, records followed by max(count)
+exception rows.  CompactRecordLayout.unpack rebuilds the dataset the full format returns, bit for bit; next_obs is
+materialised (one copy of the obs slice), every other field stays a view.  For config 5: 121 x 8192 x 26 floats = 103 MB
+plus 80 bytes per exception row sent per rank, instead of 173 MB.
 """
 import torch
 import torch.distributed as dist
@@ -60,6 +69,84 @@ class RecordLayout:
         return idx[None, :] < torch.tensor(self.sizes, device=device)[:, None]
 
 
+class CompactRecordLayout(RecordLayout):
+    """The compact record format (BatchedAtacomEnv.rollout_compact, include/atacom_hip.h: atacom_rollout_compact) of a
+    collection of T = n_steps steps: per rank, records [T + 1, Bm, Fc] with Fc = D + k + 3 --
+    rows 0..T-1 [obs | action | reward | absorbing | last], row T the tail [obs after step T-1 | zeros] -- and a list of
+    exception rows [t, b, terminal obs] (D + 2 floats) for the episode ends at t < T-1 of auto-resetting engines.
+    `unpack` rebuilds exactly what RecordLayout.unpack returns for the full format.  time_major / valid_mask as there."""
+
+    def __init__(self, sizes, obs_dim, n_null, n_steps):
+        super().__init__(sizes, obs_dim, n_null)
+        self.T = int(n_steps)
+        self.Fc = self.D + self.k + 3
+        self.E = self.D + 2                                   # floats per exception row
+        self.record_numel = (self.T + 1) * self.Bm * self.Fc  # elements of one rank's records
+
+    def unpack(self, records, ends=None, n_ends=None):
+        """records [W, T + 1, Bm, Fc] (or [T + 1, Bm, Fc] for one rank), ends [W, M, D + 2] (or [M, D + 2]) of which the
+        first n_ends[r] rows of block r are valid (None: all M) -> the dict of RecordLayout.unpack, [W, T, Bm, ...] (or
+        [T, Bm, ...]).  Every field but next_obs is a view; next_obs is materialised: next_obs[t] = obs[t + 1],
+        next_obs[T-1] = the tail, then each exception row overwrites its (t, b).  The order of the exception rows does not
+        matter, and a superset of the necessary rows (any rows of last = 1) gives the same result."""
+        one = records.dim() == 3
+        if one:
+            records = records.unsqueeze(0)
+            ends = None if ends is None else ends.unsqueeze(0)
+            n_ends = None if n_ends is None else [n_ends]
+        D, k, T = self.D, self.k, self.T
+        if records.dim() != 4 or records.shape[1] != T + 1 or records.shape[3] != self.Fc:
+            raise ValueError("compact records must be [W, %d, Bm, %d], got %s" % (T + 1, self.Fc, tuple(records.shape)))
+        body = records[:, :T]
+        nobs = records[:, 1:, :, :D].clone()                 # obs of the next step; the tail row closes the last step
+        if ends is not None and ends.shape[1] > 0:
+            W, M = ends.shape[0], ends.shape[1]
+            if ends.shape[2] != self.E:
+                raise ValueError("exception rows must hold %d floats, got %d" % (self.E, ends.shape[2]))
+            counts = [M] * W if n_ends is None else [int(c) for c in n_ends]
+            if len(counts) != W or any(c < 0 or c > M for c in counts):
+                raise ValueError("n_ends %s does not fit exception blocks of %d rows for %d ranks" % (counts, M, W))
+            live = torch.arange(M, device=ends.device)[None, :] < torch.tensor(counts, device=ends.device)[:, None]
+            rows = ends[live]                                 # [N, D + 2], block by block
+            rank = torch.arange(W, device=ends.device)[:, None].expand(W, M)[live]
+            if rows.shape[0] > 0:
+                t, b = rows[:, 0].long(), rows[:, 1].long()
+                bad = (t < 0) | (t >= T) | (b < 0) | (b >= records.shape[2])
+                if bool(bad.any()):
+                    raise ValueError("an exception row names a (t, b) outside the [%d, %d] records" % (T, records.shape[2]))
+                nobs[rank.to(nobs.device), t.to(nobs.device), b.to(nobs.device)] = rows[:, 2:].to(nobs.device)
+        out = {'obs': body[..., :D], 'action': body[..., D:D + k], 'reward': body[..., D + k], 'next_obs': nobs,
+               'absorbing': body[..., D + k + 1] > 0.5, 'last': body[..., D + k + 2] > 0.5}
+        return {key: v[0] for key, v in out.items()} if one else out
+
+
+class CompactShard:
+    """One rank's compact collection (RolloutCollector with record_format='compact'): `records` [T + 1, Bm, Fc] and `ends`
+    [capacity, D + 2] are views into ONE flat buffer, records first, so that the records and the first rows of the exception
+    list form a contiguous send segment; the first `n_ends` rows of `ends` are valid."""
+
+    def __init__(self, flat, layout, capacity, n_ends=0):
+        self.flat, self.layout, self.capacity, self.n_ends = flat, layout, int(capacity), int(n_ends)
+        lay = layout
+        self.records = flat[:lay.record_numel].view(lay.T + 1, lay.Bm, lay.Fc)
+        self.ends = flat[lay.record_numel:lay.record_numel + self.capacity * lay.E].view(self.capacity, lay.E)
+
+
+class CompactGather:
+    """A gathered compact collection: `flat` [W, L] holds every rank's records followed by max(n_ends) exception rows (those
+    past a rank's own count are zero); `n_ends` lists the valid rows per rank."""
+
+    def __init__(self, flat, layout, n_ends):
+        self.flat, self.layout, self.n_ends = flat, layout, list(n_ends)
+
+    def unpack(self):
+        lay, W = self.layout, self.flat.shape[0]
+        M = max(self.n_ends) if self.n_ends else 0
+        rec = self.flat[:, :lay.record_numel].view(W, lay.T + 1, lay.Bm, lay.Fc)
+        ends = self.flat[:, lay.record_numel:lay.record_numel + M * lay.E].view(W, M, lay.E)
+        return lay.unpack(rec, ends, self.n_ends)
+
+
 class RolloutCollector:
     """Drive one local engine (a BatchedAtacomEnv, or anything with its surface) and assemble global rollouts.
 
@@ -67,9 +154,18 @@ class RolloutCollector:
     group        : torch.distributed process group (None = default group; no-op if dist is not initialised)
     global_batch : total number of envs over all ranks (default env.batch * world, i.e. equal shards); ragged
                    shards follow shard_bounds(global_batch, world, rank) and are padded to the largest shard
+    record_format: 'full' (default) -- the packed records [T, Bm, 2 D + k + 3] all-gathered as they are; 'compact' -- records
+                   without next_obs plus the exception rows of the episode ends (CompactRecordLayout): D fewer floats per
+                   record sent, the same dataset returned.  Compact costs one stream synchronisation per collection (the
+                   exception counts are exchanged before the records): when collect_async returns, the rollout kernel has
+                   finished.
     """
 
-    def __init__(self, env, group=None, global_batch=None, force_collective=False):
+    def __init__(self, env, group=None, global_batch=None, force_collective=False, record_format='full'):
+        if record_format not in ('full', 'compact'):
+            raise ValueError("record_format must be 'full' or 'compact', got %r" % (record_format,))
+        self.record_format = record_format
+        self.last_gather_bytes = 0                # payload one rank sent in the last gather (its send buffer)
         self.env = env
         self.group = group
         # force_collective: run the collectives even in a world of one rank (they are a copy through the backend then):
@@ -91,8 +187,10 @@ class RolloutCollector:
         self.k = env.dims['null']
         self.D = env.obs_dim
         self.F = 2 * self.D + self.k + 3          # obs, action, reward, next_obs, absorbing, last
+        self.Fc = self.D + self.k + 3             # the compact record: the same minus next_obs
         self.layout = RecordLayout(self.sizes, self.D, self.k)
         self._recv = None
+        self._recv_flat = None
         self.mappings = self._agree_on_mappings()
 
     def _agree_on_mappings(self):
@@ -139,12 +237,15 @@ class RolloutCollector:
 
     # ------------------------------------------------------------------ local collection
     def collect_local(self, n_steps, actions=None, policy=None, noise=None, out=None):
-        """T = n_steps env steps of the local shard -> packed records [T, Bm, F].
+        """T = n_steps env steps of the local shard -> packed records [T, Bm, F] (record_format 'full') or a CompactShard
+        (record_format 'compact'; `out` is then a flat contiguous buffer of at least compact_numel(T) elements).
         actions [T, B_local, k]  : pre-generated actions, ONE kernel launch;
         policy = MlpPolicy       : the actor network evaluated inside the rollout kernel, ONE launch (`noise` optional);
         policy = callable        : policy(obs) -> actions, one launch per step (host-driven loop)."""
         env = self.env
         self._check_mappings_unchanged()
+        if self.record_format == 'compact':
+            return self._collect_local_compact(n_steps, actions, policy, noise, out)
         fused = hasattr(env, 'rollout_packed')
         if fused and actions is not None:
             return env.rollout_packed(actions=actions, out=out, batch_stride=self.Bm)
@@ -152,29 +253,7 @@ class RolloutCollector:
             return env.rollout_packed(policy=policy, n_steps=n_steps, noise=noise, out=out, batch_stride=self.Bm)
         # engines without the packed kernel (the CPU test double) and host-side policies: pack here
         B = env.batch
-        if actions is not None:
-            o = env.rollout(actions)
-            obs, nobs, rew = o['obs'], o['next_obs'], o['reward']
-            ab, last, act = o['absorbing'], o['last'], o['action']
-        else:
-            assert policy is not None
-            obs_l, act_l, rew_l, nobs_l, ab_l, last_l = [], [], [], [], [], []
-            o = env.reset()
-            for _ in range(n_steps):
-                a = policy(o)
-                no, r, absorbing, info = env.step(a)
-                obs_l.append(o); act_l.append(torch.as_tensor(a, dtype=no.dtype, device=no.device))
-                rew_l.append(r); nobs_l.append(no); ab_l.append(absorbing); last_l.append(info['last'])
-                o = no
-                if bool(info['last'].any()):
-                    # mushroom_rl.Core resets finished episodes between steps; engines created with
-                    # auto_reset=True have already done it on the device, others get a masked reset
-                    if not getattr(env, 'cfg', None) or not env.cfg.auto_reset:
-                        o = env.reset(mask=info['last'])
-                    else:
-                        o = env.reset(mask=torch.zeros_like(info['last']))
-            obs, act, rew = torch.stack(obs_l), torch.stack(act_l), torch.stack(rew_l)
-            nobs, ab, last = torch.stack(nobs_l), torch.stack(ab_l), torch.stack(last_l)
+        obs, act, rew, nobs, ab, last = self._host_rollout(n_steps, actions, policy)
         T = obs.shape[0]
         buf = torch.zeros((T, self.Bm, self.F), device=obs.device, dtype=obs.dtype) if out is None else out
         if out is not None and self.Bm > B:
@@ -188,6 +267,87 @@ class RolloutCollector:
         buf[:, :B, 2 * D + k + 2] = last.to(obs.dtype)
         return buf
 
+    def _host_rollout(self, n_steps, actions, policy):
+        """The (obs, action, reward, next_obs, absorbing, last) arrays [T, B, ...] of an engine without the packed kernels
+        or of a host-side policy."""
+        env = self.env
+        if actions is not None:
+            o = env.rollout(actions)
+            return o['obs'], o['action'], o['reward'], o['next_obs'], o['absorbing'], o['last']
+        assert policy is not None
+        obs_l, act_l, rew_l, nobs_l, ab_l, last_l = [], [], [], [], [], []
+        o = env.reset()
+        for _ in range(n_steps):
+            a = policy(o)
+            no, r, absorbing, info = env.step(a)
+            obs_l.append(o); act_l.append(torch.as_tensor(a, dtype=no.dtype, device=no.device))
+            rew_l.append(r); nobs_l.append(no); ab_l.append(absorbing); last_l.append(info['last'])
+            o = no
+            if bool(info['last'].any()):
+                # mushroom_rl.Core resets finished episodes between steps; engines created with
+                # auto_reset=True have already done it on the device, others get a masked reset
+                if not getattr(env, 'cfg', None) or not env.cfg.auto_reset:
+                    o = env.reset(mask=info['last'])
+                else:
+                    o = env.reset(mask=torch.zeros_like(info['last']))
+        return (torch.stack(obs_l), torch.stack(act_l), torch.stack(rew_l), torch.stack(nobs_l), torch.stack(ab_l),
+                torch.stack(last_l))
+
+    def compact_layout(self, n_steps):
+        return CompactRecordLayout(self.sizes, self.D, self.k, n_steps)
+
+    def compact_numel(self, n_steps):
+        """Elements of one rank's compact send buffer for T = n_steps: the records and the worst case of exception rows,
+        (T - 1) Bm (only the rows used are sent)."""
+        lay = self.compact_layout(n_steps)
+        return lay.record_numel + max(lay.T - 1, 0) * self.Bm * lay.E
+
+    def _collect_local_compact(self, n_steps, actions, policy, noise, out):
+        env = self.env
+        T = int(actions.shape[0]) if actions is not None else int(n_steps)
+        lay = self.compact_layout(T)
+        cap = max(T - 1, 0) * self.Bm           # >= every rank's count: the gather pads every rank to the largest one
+        need = lay.record_numel + cap * lay.E
+        fused = hasattr(env, 'rollout_compact') and (actions is not None or hasattr(policy, 'as_struct'))
+        if out is not None:
+            if out.dim() != 1 or out.numel() < need or not out.is_contiguous():
+                raise ValueError("out must be a flat contiguous tensor of at least %d elements" % need)
+            flat = out[:need]
+        else:
+            dt = getattr(env, 'dtype', None)
+            dev = getattr(env, 'device', torch.device('cpu'))
+            flat = torch.empty((need,), device=dev, dtype=dt) if (fused or dt is not None) else None
+        if fused:
+            sh = CompactShard(flat, lay, cap)
+            _, _, n = env.rollout_compact(actions=actions, policy=None if actions is not None else policy, n_steps=T,
+                                          noise=noise, out=(sh.records, sh.ends), batch_stride=self.Bm, ends_capacity=cap)
+            sh.n_ends = n
+            return sh
+        # engines without the compact kernel and host-side policies: pack here, listing every last row before the final
+        # step (a superset of the auto-resets; the reconstruction is the same for any superset)
+        B, D, k = env.batch, self.D, self.k
+        obs, act, rew, nobs, ab, last = self._host_rollout(T, actions, policy)
+        if flat is None:
+            flat = torch.empty((need,), device=obs.device, dtype=obs.dtype)
+        sh = CompactShard(flat, lay, cap)
+        rec = sh.records
+        rec.zero_()
+        rec[:T, :B, :D] = obs
+        rec[:T, :B, D:D + k] = act
+        rec[:T, :B, D + k] = rew
+        rec[:T, :B, D + k + 1] = ab.to(obs.dtype)
+        rec[:T, :B, D + k + 2] = last.to(obs.dtype)
+        rec[T, :B, :D] = nobs[T - 1]
+        tb = torch.nonzero(last[:T - 1].to(torch.bool))           # [n, 2] = (t, b)
+        n = int(tb.shape[0])
+        if n:
+            e = sh.ends[:n]
+            e[:, 0] = tb[:, 0].to(obs.dtype)
+            e[:, 1] = tb[:, 1].to(obs.dtype)
+            e[:, 2:] = nobs[tb[:, 0], tb[:, 1]]
+        sh.n_ends = n
+        return sh
+
     # ------------------------------------------------------------------ the one collective
     def gather(self, buf, out=None, async_op=False):
         """All-gather the packed rollout: [T, Bm, F] on every rank -> [W, T, Bm, F] on every rank, rank r's shard in
@@ -195,7 +355,11 @@ class RolloutCollector:
         Without `out` the result lives in a buffer the collector keeps and REUSES: the next gather overwrites it (an
         on-policy learner consumes a dataset before collecting the next one); pass `out` or clone to keep it.
         async_op=True returns (result, work): the collective runs on the backend's own stream (RCCL) while the caller
-        goes on -- e.g. launches the next rollout -- and `work.wait()` orders the result before its first use."""
+        goes on -- e.g. launches the next rollout -- and `work.wait()` orders the result before its first use.
+        A CompactShard (record_format 'compact') is gathered by gather_compact."""
+        if isinstance(buf, CompactShard):
+            return self.gather_compact(buf, out=out, async_op=async_op)
+        self.last_gather_bytes = buf.numel() * buf.element_size()
         if self.world == 1 and not (self.force_collective and self.distributed):
             if out is not None:
                 out.view(buf.shape).copy_(buf)
@@ -221,8 +385,59 @@ class RolloutCollector:
         work = dist.all_gather_into_tensor(out.view(self.world * T, Bm, F), buf, group=self.group, async_op=async_op)
         return (out, work) if async_op else out
 
+    def gather_compact(self, sh, out=None, async_op=False):
+        """All-gather a CompactShard: ONE all-gather of the W exception counts, then ONE all-gather of every rank's flat
+        segment -- its records followed by max(n_ends) exception rows, those past its own count zeroed -- into [W, L].
+        Returns a CompactGather (unpack() gives the dataset).  `out`: a flat contiguous tensor of at least W L elements
+        (L = records + max(n_ends) rows; W * compact_numel(T) always suffices); without it the collector reuses a buffer of
+        its own, as gather() does."""
+        lay, n = sh.layout, sh.n_ends
+        collective = not (self.world == 1 and not (self.force_collective and self.distributed))
+        gloo = collective and dist.get_backend(self.group) == 'gloo'
+        if collective:
+            dev = torch.device('cpu') if gloo else sh.flat.device
+            mine = torch.tensor([n], dtype=torch.int64, device=dev)
+            allc = torch.empty((self.world,), dtype=torch.int64, device=dev)
+            dist.all_gather_into_tensor(allc, mine, group=self.group)
+            counts = [int(c) for c in allc.cpu()]
+        else:
+            counts = [n]
+        M = max(counts)
+        if M > sh.capacity:
+            raise ValueError("a rank produced %d exception rows, more than this rank's buffer holds (%d)" % (M, sh.capacity))
+        L = lay.record_numel + M * lay.E
+        if M > n:
+            sh.flat[lay.record_numel + n * lay.E:L].zero_()
+        send = sh.flat[:L]
+        self.last_gather_bytes = L * send.element_size()
+        W = self.world
+        if out is not None and (out.dim() != 1 or out.numel() < W * L or out.dtype != send.dtype or not out.is_contiguous()):
+            raise ValueError("out must be a flat contiguous %s tensor of at least %d elements" % (send.dtype, W * L))
+        if not collective:
+            res = send.view(1, L) if out is None else out[:L].copy_(send).view(1, L)
+            g = CompactGather(res, lay, counts)
+            return (g, _Done()) if async_op else g
+        if send.is_cuda and gloo:
+            host = torch.empty((W * L,), dtype=send.dtype)
+            dist.all_gather_into_tensor(host, send.cpu(), group=self.group)
+            res = host.to(send.device) if out is None else out[:W * L].copy_(host)
+            g = CompactGather(res.view(W, L), lay, counts)
+            return (g, _Done()) if async_op else g
+        if out is None:
+            r = self._recv_flat
+            if r is None or r.numel() < W * L or r.dtype != send.dtype or r.device != send.device:
+                self._recv_flat = torch.empty((W * L,), device=send.device, dtype=send.dtype)
+            out = self._recv_flat
+        dst = out[:W * L]
+        work = dist.all_gather_into_tensor(dst, send, group=self.group, async_op=async_op)
+        g = CompactGather(dst.view(W, L), lay, counts)
+        return (g, work) if async_op else g
+
     def unpack(self, g):
-        """Views (no copy) into gathered records [W, T, Bm, F]: every entry is [W, T, Bm, ...]."""
+        """Views (no copy) into gathered records [W, T, Bm, F]: every entry is [W, T, Bm, ...].  A CompactGather unpacks
+        to the same dict (next_obs materialised, CompactRecordLayout.unpack)."""
+        if isinstance(g, CompactGather):
+            return g.unpack()
         return self.layout.unpack(g)
 
     def time_major(self, data):
