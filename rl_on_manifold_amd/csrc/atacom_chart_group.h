@@ -1,11 +1,16 @@
-// Third form of the canonical chart's lane-group kernels (LG = 2 / 4 / 8 lanes per environment; round 4).
+// The canonical chart (atacom_chart.h) distributed over the LG = 2 / 4 / 8 lanes of a group.
 //
-// Same recursion, same decisions as canonical_mu / canonical_mu_group (atacom_chart.h; specification
-// oracle/canonical_chart.py; reference semantics outside the chart's tolerance band: null_space_coordinate.py:40-79,
-// atacom.py:127-133).  What changed is WHO computes what.  Measured on the bench workload (8192 iiwa environments, 8 lanes,
-// profiles/r04_bench_probe_baseline.log): the data-dependent parts are not rare there -- the reset pose stands 7 cm from
-// the table's near boundary, so under random actions 79 % of the wavefronts run a stiff-row step and 85 % slack stage B in
-// (nearly) every sub-step -- and a third of the plain path was a prologue every lane of a group repeated.  Now:
+// Same recursion, same decisions as canonical_mu (atacom_chart.h; specification oracle/canonical_chart.py; reference
+// semantics outside the chart's tolerance band: null_space_coordinate.py:40-79, atacom.py:127-133).  The vectors
+// v_i = R^T e_i of the square-root form are DISTRIBUTED: coordinate i of the extended state -- its vector, x_i and U_i --
+// lives in lane i % LG, slot i / LG (8 lanes: one vector per lane for the iiwa task).  A projection step is then local work
+// on the own vector(s) once w is known to every lane: a broadcast from its owner when w is one of the vectors (the joint
+// steps), a group sum when it is a combination (a constraint row).  Cross-lane traffic: DPP broadcasts / butterfly sums
+// (atacom_quad.h) and, in slack stage B, one ds_bpermute gather of the longest vector (its owner is data dependent).
+// The data-dependent parts are not rare on the bench workload (8192 iiwa environments, 8 lanes,
+// profiles/r04_bench_probe_baseline.log): the reset pose stands 7 cm from the table's near boundary, so under random
+// actions 79 % of the wavefronts run a stiff-row step and 85 % slack stage B in (nearly) every sub-step.  So the prologue
+// is shared by the lanes of a group rather than repeated by each, and the per-row work is spread as well:
 //   * OWN COLUMNS.  Lane l keeps column i = LG sl + l of A = K J (At[sl][r]; built once per env step, A is held over
 //     the sub-steps).  The coefficient with which coordinate i enters a row functional is then a register, not a one-hot
 //     blend over the row (eight multiply-adds per functional, 66 + 22 per stiff-row step).
@@ -13,18 +18,45 @@
 //     b = sum A_g^T y_g / s_g^2 from its own column of A; the lower triangle is gathered (21 broadcasts) for the replicated
 //     6 x 6 Cholesky factor -- instead of every lane accumulating all 21 + 6 entries.
 //   * NO INVERSE FACTOR.  v_i = L^-1 e_i is a forward substitution with the lane's own unit vector (the one-hot of its
-//     position): 21 instructions instead of the replicated inverse (50) plus the blends that picked its column (64).
-//     x_0 = -Gamma b: z = L^-1 b as the group sum of b_i v_i, then x_i = -v_i . z.
-//   * ROW SLOTS ALWAYS.  Inequality row g belongs to lane g % LG, slot g / LG (as in the second form), but its copy of the
-//     row is built once per env step for every wavefront, and which rows are the coordinate slack / already taken travels
-//     as two bit masks tested against the lane's own bit -- no boolean blends (the second form built the slots inside the
-//     stage-B branch, 150 instructions each time, to spare quiet wavefronts; on the bench workload that branch is the rule).
+//     position): 21 instructions instead of a replicated inverse (50) plus the blends that picked its column (64).
+//     x_0 = -Gamma b: z = L^-1 b by forward substitution on the gathered b, then x_i = -v_i . z.
+//   * ROW SLOTS.  Inequality row g belongs to lane g % LG, slot g / LG: what the rows contribute one by one -- the column
+//     tests of the slack stages, the slack velocities of the assembly -- a lane does for its own rows only (ceil(NG / LG)
+//     slots instead of NG rows).  Its copy of the row is built once per env step for every wavefront; which rows are the
+//     coordinate slack / already taken travels as two bit masks tested against the lane's own bit, and the passing columns
+//     as ONE group-summed number (bit g = column g, disjoint powers of two: exact).
 //   * the equality row's final exact correction works on the distributed coordinates (two group sums) before they are
-//     gathered, instead of on replicated copies after.
-// Everything a decision depends on is replicated or group-summed, so the lanes of a group still agree bit for bit.
+//     gathered.
+// Everything a decision depends on is replicated or group-summed, so the lanes of a group agree bit for bit.
+// Measured against the removed earlier forms: profiles/r03_ab_rowslots.log, r03_ab_stage_a.log, r04_ab_chart_form.log.
 #pragma once
 
 namespace atacom {
+
+// v as lane src_lane of the wavefront holds it (ds_bpermute: the source may differ per lane and be data dependent)
+template <typename T>
+__device__ __forceinline__ T lane_gather(T v, int src_lane) {
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
+    } else {
+        const long long b = __builtin_bit_cast(long long, v);
+        const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, (int)(b & 0xffffffffll));
+        const int hi = __builtin_amdgcn_ds_bpermute(src_lane << 2, (int)(b >> 32));
+        return __builtin_bit_cast(T, ((long long)hi << 32) | (unsigned int)lo);
+    }
+}
+
+// max over the group, in all its lanes (the butterfly of qsum, atacom_quad.h)
+template <int LN, typename T>
+__device__ __forceinline__ T qmax(T v) {
+    const T s1 = num<T>::max(v, dpp_mov<0xB1>(v));
+    if constexpr (LN == 2) return s1;
+    else {
+        const T s2 = num<T>::max(s1, dpp_mov<0x4E>(s1));
+        if constexpr (LN == 4) return s2;
+        else return num<T>::max(s2, dpp_mov<DPP_ROW_HALF_MIRROR>(s2));
+    }
+}
 
 // Cholesky factor of the SPD matrix whose LOWER triangle is Ml (replicated): L and 1 / L_jj.
 template <typename T, int N>
@@ -155,7 +187,7 @@ __device__ __forceinline__ void gsum_all(T (&w)[N]) {
     }
 }
 
-template <typename T, typename E, int LG, bool STATIC_A = false>
+template <typename T, typename E, int LG>
 __device__ __forceinline__ void canonical_mu_group3(const T (&A)[E::NC][E::NQ], const ChartPre<T, E, LG>& cp,
                                                     const T (&arow)[E::NG], const T (&s)[E::NG], const T (&y)[E::NC],
                                                     const T (&alpha)[E::NK], const T tol, T (&mu)[E::NN],
@@ -238,8 +270,8 @@ __device__ __forceinline__ void canonical_mu_group3(const T (&A)[E::NC][E::NQ], 
     // soft row of weight 1 / s^2 ~ 10^3 the entries of b are ~10^4 and cancel in z_k = (b_k - L_k0 z_0 - ...) / L_kk down to
     // O(10): every separately rounded product left 6e-8 x 10^4 in z, x_0 inherited it, and the slack velocity
     // w_g = -(y_g + A_g x) / s_g amplified it by 1 / s_g.  The planar float32 soak caught it: 64 samples of 295 k beyond the
-    // quick sensitivity bound against 1 for the second form -- whose z = Li b is one fused chain per entry, a single large
-    // rounding -- and 7 unexplained; found by giving the third form the second form's prologue piece by piece
+    // quick sensitivity bound against 1 for the earlier lane-group form -- whose z = Li b is one fused chain per entry, a
+    // single large rounding -- and 7 unexplained; found by giving this form that one's prologue piece by piece
     // (profiles/r04_chart_form3_planar.md).  In the substitution every product is fused into the running remainder: the only
     // roundings are of the small results.  Same instruction count: NQ broadcasts + NQ (NQ + 1) / 2 operations.)
     {
@@ -409,8 +441,8 @@ __device__ __forceinline__ void canonical_mu_group3(const T (&A)[E::NC][E::NQ], 
             for (int i = 0; i < NK; ++i) tv = num<T>::fma((n_acc == i) ? T(1) : T(0), alpha[i], tv);
             // ALL candidate rows at once, every lane its own (row slots): the vector of f_g = A_g u is a combination of ALL
             // vectors, so they are gathered first (N1 x N1 broadcasts) -- deterministic cost, whatever rows the environments
-            // of the wavefront are at (the second form walked the rows: 80 instructions per row looked at, 190 per trip of
-            // the per-lane scan, the passing column typically a late one)
+            // of the wavefront are at (walking the rows instead cost 80 instructions per row looked at, 190 per trip of a
+            // per-lane scan, the passing column typically a late one)
             T Uall[N1];
             static_for<0, N1>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;

@@ -1,18 +1,15 @@
-// Row N4, round 5: the rigid-body recursions of the iiwa + striker chain IN LINK COORDINATES ("the
-// candidate" of round 4's list).
+// Row N4: the rigid-body recursions of the iiwa + striker chain IN LINK COORDINATES (round 5).
 //
-// atacom_dynamics.h evaluates recursive Newton-Euler and the composite-rigid-body mass matrix in WORLD coordinates: it first
-// builds, per physics sub-step, the world frame of all nine bodies -- joint axes, origins, centres of mass and R I R^T of
-// every inertia tensor: 135 live values, 9 x 45 operations for the tensors alone -- and the kernels that call it run at the
-// edge of the register file (LDS parking of the solver state, scratch in the lane mapping).  Here every quantity of body i
-// lives in body i's own joint frame:
+// Recursive Newton-Euler and the composite-rigid-body mass matrix (Featherstone 2008).  Every quantity of body i lives in
+// body i's own joint frame (the earlier world-coordinate form built the world frame of all nine bodies per physics
+// sub-step, 135 live values, and ran its kernels at the edge of the register file):
 //   * inertia tensors, centres of mass and the bodies' own composite inertias are INSTRUCTION LITERALS (atacom_iiwa_inertia.h);
 //   * a joint is "translate along one axis of the parent, a signed permutation of the axes, a plane rotation by q_i"
 //     (urdf/iiwa_1.urdf:72,110,147,184,221,258,295; the striker's universal joint :380-399): moving a vector across a joint
 //     costs four multiply-adds, a symmetric tensor twelve; cross products with the joint offset touch two components;
 //   * nothing of the chain is kept but the nine sines / cosines.
-// Same equations as oracle/dynamics.py (rnea, mass_matrix), which golden set G11 pins to the reference's URDF: the tests
-// compare the float64 build at 1e-10 (tests/test_gpu_dynamics.py).
+// Same equations as oracle/dynamics.py (rnea, mass_matrix; the readable world-coordinate statement), which golden set G11
+// pins to the reference's URDF: the tests compare the float64 build at 1e-10 (tests/test_gpu_dynamics.py).
 // What the reference does with them: PyBullet calculateInverseDynamics (iiwa_hit_atacom.py:58-63) and stepSimulation.
 #pragma once
 #include "atacom_linalg.h"
@@ -21,22 +18,11 @@
 namespace atacom {
 namespace lk {
 
-// -DATACOM_LK_FENCE=1: a scheduling barrier after every body of the recursions (tuning: keeps the scheduler from interleaving
-// bodies, i.e. from stretching live ranges, in kernels at the edge of the register file)
-#ifndef ATACOM_LK_FENCE
-#define ATACOM_LK_FENCE 0
-#endif
-#if ATACOM_LK_FENCE
-#define ATACOM_LK_BODY() __builtin_amdgcn_sched_barrier(0)
-#else
-#define ATACOM_LK_BODY() ((void)0)
-#endif
-
 // ---- joint descriptors.  Joint i maps parent coordinates v to child coordinates v' by
 //   u_k = SG[k] v[PM[k]]   (signed permutation),   v'_A = c u_A + s u_B,   v'_B = c u_B - s u_A,   v'_C = u_C
 // with (c, s) = cos / sin q_i; C is the joint axis in the child's (and, through the permutation, the parent's) frame.
 // Arm joints 0..6: kinds of atacom_envs.h (0: identity, 1: u = (-x, z, y), 2: u = (x, z, -y)), rotation about the local z.
-// Joint 7 (striker_joint_1): about the local y; joint 8 (striker_joint_2): about the local x (atacom_dynamics.h).
+// Joint 7 (striker_joint_1): about the local y; joint 8 (striker_joint_2): about the local x (urdf:383,396).
 constexpr int PM[9][3] = {{0, 1, 2}, {0, 2, 1}, {0, 2, 1}, {0, 2, 1}, {0, 2, 1}, {0, 2, 1}, {0, 2, 1}, {0, 1, 2}, {0, 1, 2}};
 constexpr int SG[9][3] = {{1, 1, 1}, {-1, 1, 1}, {-1, 1, 1}, {1, 1, -1}, {-1, 1, 1}, {1, 1, -1}, {-1, 1, 1}, {1, 1, 1}, {1, 1, 1}};
 constexpr int PA[9] = {0, 0, 0, 0, 0, 0, 0, 2, 1};
@@ -188,7 +174,6 @@ __device__ __forceinline__ void rnea9(const Trig9<T>& g, const T (&dq)[9], const
         crossv(w, Iw, t1);
 #pragma unroll
         for (int k = 0; k < 3; ++k) Nm[i][k] = Ial[k] + t1[k];
-        ATACOM_LK_BODY();
     });
     // tip to base: (f, n) of the subtree beyond joint i, in body i's frame, n about joint i's origin
     T f[3] = {T(0), T(0), T(0)}, n[3] = {T(0), T(0), T(0)};
@@ -214,14 +199,15 @@ __device__ __forceinline__ void rnea9(const Trig9<T>& g, const T (&dq)[9], const
 #pragma unroll
             for (int k = 0; k < 3; ++k) { f[k] = fp[k]; n[k] = np[k]; }
         }
-        ATACOM_LK_BODY();
     });
 }
 
 // Mass-matrix entries Ml[i][j] (j <= i, j < NB) for the rows i < NR, and optionally the diagonal entries of the rows >= NB
-// (dg[i - NB]) -- the interface of atacom_dynamics.h's crba.  Composite inertias (mass, first moment, inertia about the
-// joint origin) are carried from the tip towards the base in link coordinates; row i is the momentum (p, L) of composite i
-// under joint i's unit velocity, walked down the chain: M_ij = e_C(j) . L in frame j.
+// (dg[i - NB]).  NR = NB gives the leading block of the controlled joints; NR = 9 adds the coupling rows of the three servo
+// joints (M[6..8][0..5]: their accelerations go to the right-hand side of the controlled joints' equation).  Composite
+// inertias (mass, first moment, inertia about the joint origin) are carried from the tip towards the base in link
+// coordinates; row i is the momentum (p, L) of composite i under joint i's unit velocity, walked down the chain:
+// M_ij = e_C(j) . L in frame j.
 template <typename T, int NB, int NR = NB>
 __device__ __forceinline__ void crba(const Trig9<T>& g, T (&Ml)[NR][NB], T* dg = nullptr) {
     static_assert(NR >= NB && NR <= 9, "");
@@ -287,7 +273,6 @@ __device__ __forceinline__ void crba(const Trig9<T>& g, T (&Ml)[NR][NB], T* dg =
                 if constexpr (k - 1 < NB) Ml[i][k - 1] = L[PC[k - 1]];
             });
         }
-        ATACOM_LK_BODY();
     });
 }
 

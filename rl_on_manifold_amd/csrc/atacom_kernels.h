@@ -20,10 +20,6 @@
 namespace atacom {
 
 constexpr int WAVE = 64;
-// rigid-body kernels: park the held solver state in LDS across the dynamics (env_step); -DATACOM_DYN_PARK=0: the A/B build
-#ifndef ATACOM_DYN_PARK
-#define ATACOM_DYN_PARK 0           // round 5: off -- with the dynamics in link coordinates (atacom_dynamics_link.h) the quad kernels
-#endif                              // fit without it (no scratch, 130 AGPRs) and run 42.7 instead of 45.6 us per step
 // threads per workgroup of the step / rollout kernels: the quad mapping runs 2.7 % faster with four waves per
 // workgroup (one per SIMD of a CU, sharing the instruction cache), the lane mapping with one (measured, profiles/)
 #ifndef ATACOM_BLOCK_GROUP
@@ -377,23 +373,18 @@ __device__ __forceinline__ void reset_env(const Params<T>& P, const Ref& ref, En
 //           dynamics_mode 2: for [ddq, dds] -- the controller knows what the servo joints are about to do (feed-forward
 //           of their reaction on the arm; NOT what the reference computes);
 //   ddq   = M_aa^-1 (tau - rnea_a(q, dq, [0; dds]) - D_a dq_a)       (hybrid forward dynamics, URDF joint damping).
-// LINK: the recursions in link coordinates (atacom_dynamics_link.h, round 5) or in world coordinates (atacom_dynamics.h).
-template <typename T, typename E, bool LINK = true>
+// The recursions run in link coordinates (atacom_dynamics_link.h).  (No scheduling barriers between the passes: they only pin
+// the allocator -- with them the lane-mapped single-step kernel took 76 scratch accesses INSIDE THE SOLVER block, 73 -> 83 us
+// per step.)
+template <typename T, typename E>
 __device__ __forceinline__ void rigid_body_substep(const Params<T>& P, EnvState<T, E>& st, T (&ddq)[E::NQ]) {
     static_assert(E::NQ == 6, "iiwa only");
-    // phase boundaries (scheduling barriers) belong to the world-coordinate form, whose three passes together overflow the
-    // register file when interleaved; around the link-coordinate form they only pin the allocator: with them the lane-mapped
-    // single-step kernel takes 76 scratch accesses INSIDE THE SOLVER block (73 -> 83 us per step), without them none
-#ifndef ATACOM_LK_PHASE
-#define ATACOM_LK_PHASE 0
-#endif
-    auto phase = [] { if constexpr (!(LINK && ATACOM_DYN_LINK) || ATACOM_LK_PHASE) ATACOM_PHASE(); };
     T q9[9], dq9[9];
 #pragma unroll
     for (int i = 0; i < 6; ++i) { q9[i] = st.q[i]; dq9[i] = st.dq[i]; }
 #pragma unroll
     for (int i = 0; i < 3; ++i) { q9[6 + i] = st.qx[i]; dq9[6 + i] = st.dqx[i]; }
-    ATACOM_MARK("DYN_chain"); phase();
+    ATACOM_MARK("DYN_chain");
     // The equation of motion is linear in the accelerations, tau = M(q) ddq + h(q, dq), so ONE recursive Newton-Euler
     // pass (h: all accelerations zero) and the mass-matrix rows the step needs anyway replace the two passes of the literal
     // formulation (inverse dynamics of the planned acceleration; bias with the servo joints' accelerations):
@@ -404,26 +395,14 @@ __device__ __forceinline__ void rigid_body_substep(const Params<T>& P, EnvState<
     for (int i = 0; i < 9; ++i) zero9[i] = T(0);
     T Ml[9][6], Mss[3];                             // rows 0..5: M_cc (lower triangle); rows 6..8: M_sc = M_cs^T
     T z6[3], z7[3], y7[3];                          // world axes behind the servo set-points
-    if constexpr (LINK && ATACOM_DYN_LINK) {
-        lk::Trig9<T> tg;
-        lk::trig9(q9, tg);
-        ATACOM_MARK("DYN_rnea"); phase();
-        lk::rnea9<T, true>(tg, dq9, zero9, h9);
-        ATACOM_MARK("DYN_crba"); phase();
-        lk::crba<T, 6, 9>(tg, Ml, Mss);
-        ATACOM_MARK("DYN_servo"); phase();
-        lk::servo_axes(tg, z6, z7, y7);
-    } else {
-        Chain9<T> ch;
-        iiwa_chain9(q9, ch);
-        ATACOM_MARK("DYN_rnea"); phase();
-        rnea9<T, true>(ch, dq9, zero9, h9);
-        ATACOM_MARK("DYN_crba"); phase();
-        crba<T, 6, 9>(ch, Ml, Mss);
-        ATACOM_MARK("DYN_servo"); phase();
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { z6[d] = ch.a[5][d]; z7[d] = ch.a[6][d]; y7[d] = ch.a[7][d]; }
-    }
+    lk::Trig9<T> tg;
+    lk::trig9(q9, tg);
+    ATACOM_MARK("DYN_rnea");
+    lk::rnea9<T, true>(tg, dq9, zero9, h9);
+    ATACOM_MARK("DYN_crba");
+    lk::crba<T, 6, 9>(tg, Ml, Mss);
+    ATACOM_MARK("DYN_servo");
+    lk::servo_axes(tg, z6, z7, y7);
     const T tgt[3] = {joint7_target(z6, z7, st.qx[0]), universal_target(z7, y7), T(0)};
     constexpr T vmax[3] = {T(1.5 * 2.356194490192345), T(1.5 * 3.1415926), T(1.5 * 3.1415926)};     // urdf:297,384,397
     constexpr T effort_s[3] = {T(40), T(10), T(10)};                                                // urdf:297,384,400
@@ -454,9 +433,9 @@ __device__ __forceinline__ void rigid_body_substep(const Params<T>& P, EnvState<
         for (int s2 = 0; s2 < 3; ++s2) r = num<T>::fma(-Ml[6 + s2][i], dds[s2], r);
         rhs[i] = r;
     }
-    ATACOM_MARK("DYN_solve"); phase();
+    ATACOM_MARK("DYN_solve");
     chol_solve<T, 6, 9>(Ml, rhs);
-    ATACOM_MARK("DYN_end"); phase();
+    ATACOM_MARK("DYN_end");
 #pragma unroll
     for (int i = 0; i < 6; ++i) ddq[i] = rhs[i];
 #pragma unroll
@@ -714,7 +693,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                                // per row carried over the sub-steps instead of two)
     // hoist of the sub-step-invariant first reflector (see prepare): every mapping, ATACOM mode, held q / dq, and an
     // equality row on top of J_c (iiwa; the planar and circle J_c start with a slack-carrying row)
-    constexpr bool CANON = CHART >= 1 && E::MODE == 0;        // CHART 2 (from k_step): canonical, slack stage A in static row order
+    constexpr bool CANON = CHART >= 1 && E::MODE == 0;
     constexpr bool G0PRE = HOIST_G0 && HOLD && E::MODE == 0 && NF > 0 && NQ > 1 && !CANON;
     T arow[NG];                 // CANON: max |K J| of every inequality row (the scale its slack is compared with)
     T g0_d = T(0), g0_tau = T(0);
@@ -723,14 +702,10 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
     T Aq[NC][SQ];              // LANES > 1: this lane's columns of [K J | 0] (column c >= 1 -> lane (c-1) % LANES,
                                // slot (c-1) / LANES; column 0 is replicated and read from A directly, atacom_quad.h)
     T tlo[NQ], tup[NQ];         // acc_truncation bounds (atacom.py:117-121): functions of the controller's dq only
-    // CANON, LANES > 1 (third form, atacom_chart_group.h): the lane's own columns / rows of A, built with A
-    constexpr bool CANON3 = CANON && LANES > 1 && (ATACOM_CHART_FORM == 3);
+    // CANON, LANES > 1 (atacom_chart_group.h): the lane's own columns / rows of A, built with A
     [[maybe_unused]] ChartPre<T, E, LGC> cpre;
     // the prologue shared by the lanes of a group instead of replicated in each (iiwa_prepare_group above; round 5)
-#ifndef ATACOM_GROUP_PRE
-#define ATACOM_GROUP_PRE 1          // -DATACOM_GROUP_PRE=0: the A/B build with the replicated prologue
-#endif
-    constexpr bool GROUP_PRE = ATACOM_GROUP_PRE && E::ID == 2 && LANES == 8 && !CANON && E::MODE == 0 && !DYN;
+    constexpr bool GROUP_PRE = E::ID == 2 && LANES == 8 && !CANON && E::MODE == 0 && !DYN;
     auto prepare = [&](int sub) {
 #pragma unroll
             for (int i = 0; i < NQ; ++i) { qc[i] = st.q[i]; dqc[i] = st.dq[i]; }
@@ -826,7 +801,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                     arow[g] = m;
                 }
             }
-            if constexpr (CANON3) chart_prepare<T, E, LGC>(A, arow, yb, P.Kc, lq, cpre);
+            if constexpr (CANON && LANES > 1) chart_prepare<T, E, LGC>(A, arow, yb, P.Kc, lq, cpre);
             ATACOM_MARK("PRE_blend");
             if (LANES > 1 && !CANON) {
                 // this lane's columns of K J: a one-hot blend over the lane group (exact: the mask is 0 / 1 and the
@@ -882,8 +857,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
         }
         if constexpr (CANON) {
             if constexpr (LANES == 1) canonical_mu<T, E>(A, arow, st.s, y, alpha, P.rref_tol, mu ATACOM_DBG_ARG(out.dbg));
-            else if constexpr (CANON3) canonical_mu_group3<T, E, LGC, CHART == 2>(A, cpre, arow, st.s, y, alpha, P.rref_tol, mu, lq ATACOM_DBG_ARG(out.dbg));
-            else canonical_mu_group<T, E, LANES, CHART == 2>(A, arow, st.s, y, alpha, P.rref_tol, mu, lq ATACOM_DBG_ARG(out.dbg));
+            else canonical_mu_group3<T, E, LGC>(A, cpre, arow, st.s, y, alpha, P.rref_tol, mu, lq ATACOM_DBG_ARG(out.dbg));
         } else if (LANES == 1 || E::MODE != 0) {
             T x[NN], nb[NN][NN - NC], nmu[NN];
             auto aget = [&](auto rc, auto cc) -> T {
@@ -953,22 +927,16 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
             }
         } else {
             if constexpr (DYN && E::ID == 2) {
-                // row N4: ddq <- forward dynamics.  What the solver holds over the sub-steps -- the lane's columns of K J, its
-                // replicated column 0, the slack-independent right-hand side, the truncation bounds: 84 values -- is PARKED
-                // IN LDS across the rigid-body sub-step (float, reference chart): the nine-body chain, the Newton-Euler pass
-                // and the mass-matrix rows need ~300 registers of their own, and next to the held state the kernels spilled
-                // to scratch (32 - 200 bytes per lane through global memory, per sub-step).  21 ds_write_b128 + 21
-                // ds_read_b128 per sub-step instead; every lane owns its slice, no barrier.
-#ifndef ATACOM_DYN_PARK_LANE
-#define ATACOM_DYN_PARK_LANE 0      // tuning: park in the one-environment-per-lane single-step kernel as well
-#endif
-                constexpr bool PARK = std::is_same<T, float>::value && !CANON && E::MODE == 0 && (ATACOM_DYN_PARK || PARKDYN) &&
-                                      (LANES > 1 || (ATACOM_DYN_PARK_LANE && THREADS == 64));       // (one environment per lane: measured SLOWER with the parking, 73.9 ->
-                                                       // 90.7 us per step at 8192 environments -- those kernels still spill and pay
-                                                       // the LDS traffic on top; and the lane-mapped policy kernel's own 100 KB of
-                                                       // LDS would leave no room)
+                // row N4: ddq <- forward dynamics.  In the policy kernel (PARKDYN; float, reference chart, lane groups) what
+                // the solver holds over the sub-steps -- the lane's columns of K J, its replicated column 0, the
+                // slack-independent right-hand side, the truncation bounds: 84 values -- is PARKED IN LDS across the
+                // rigid-body sub-step: 21 ds_write_b128 + 21 ds_read_b128 per sub-step; every lane owns its slice, no barrier.
+                // (One environment per lane: measured SLOWER with the parking, 73.9 -> 90.7 us per step at 8192 environments
+                // -- those kernels still spill and pay the LDS traffic on top; and the lane-mapped policy kernel's own 100 KB
+                // of LDS would leave no room.)
+                constexpr bool PARK = std::is_same<T, float>::value && !CANON && E::MODE == 0 && PARKDYN && LANES > 1;
                 if constexpr (PARK) {
-                    constexpr int NV = (LANES > 1 ? NC * SQ + NC : NC * NQ) + NC + 2 * NQ, NG4 = (NV + 3) / 4;
+                    constexpr int NV = NC * (SQ + 1) + NC + 2 * NQ, NG4 = (NV + 3) / 4;
                     __shared__ float4 parked[NG4 * THREADS];
                     T pk[NG4 * 4];
                     int k = 0;
@@ -976,14 +944,9 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                         k = 0;
 #pragma unroll
                         for (int r = 0; r < NC; ++r) {
-                            if constexpr (LANES > 1) {
 #pragma unroll
-                                for (int sl = 0; sl < SQ; ++sl) f(Aq[r][sl]);
-                                f(A[r][0]);
-                            } else {
-#pragma unroll
-                                for (int c = 0; c < NQ; ++c) f(A[r][c]);
-                            }
+                            for (int sl = 0; sl < SQ; ++sl) f(Aq[r][sl]);
+                            f(A[r][0]);
                         }
 #pragma unroll
                         for (int r = 0; r < NC; ++r) f(yb[r]);
@@ -1246,9 +1209,7 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_step(const Params<T> P, T* __r
     unsigned long long ts1;
     asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts1) : "v"(st.q[0]) : "memory");
 #endif
-    // single-step launches last as long as their slowest wavefront: the canonical chart's slack stage A runs in static row
-    // order there (atacom_chart.h); the T-step kernels, which average over their steps, keep the per-lane scan
-    env_step<T, E, LANES, HOLD, DYN, true, (CHART == 1 ? 2 : CHART)>(P, st, act, out, lq, ref);
+    env_step<T, E, LANES, HOLD, DYN, true, CHART>(P, st, act, out, lq, ref);
     ATACOM_MARK("STORE");
 #ifdef ATACOM_TIMESTAMPS
     unsigned long long ts2;
@@ -1365,16 +1326,11 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_rollout(const Params<T> P, int
 // their stores masked off.
 template <typename T, typename E, int LANES, int H>
 struct MlpPath {
-    // 8 lanes per environment: a wave holds 8 environments -- half of the one GEMM block it can fill is padding.  The VALU form
-    // spread over the 8 lanes (8 hidden units per lane, -DATACOM_MLP8_VALU=1) was built and measured against it in round 6:
-    // SLOWER -- iiwa 23.7 against 23.2 us per step, planar 11.7 against 10.9, at 4096 and 8192 environments, three interleaved
-    // runs (profiles/r06_ab_mlp8_valu.log): 560 vector issue slots cost a lone wave more than 100 matrix instructions and two
-    // LDS round trips.  The matrix cores pay even half empty.
-#ifndef ATACOM_MLP8_VALU
-#define ATACOM_MLP8_VALU 0
-#endif
-    static constexpr bool MFMA = std::is_same<T, float>::value && H == 64 && E::OBS <= 32 && E::NK <= 8 &&
-                                 !(LANES == 8 && ATACOM_MLP8_VALU);
+    // 8 lanes per environment: a wave holds 8 environments -- half of the one GEMM block it can fill is padding.  A VALU form
+    // spread over the 8 lanes (8 hidden units per lane) measured SLOWER in round 6 -- iiwa 23.7 against 23.2 us per step,
+    // planar 11.7 against 10.9 (profiles/r06_ab_mlp8_valu.log): 560 vector issue slots cost a lone wave more than 100 matrix
+    // instructions and two LDS round trips.  The matrix cores pay even half empty.
+    static constexpr bool MFMA = std::is_same<T, float>::value && H == 64 && E::OBS <= 32 && E::NK <= 8;
     // blocks of 16 environments per wavefront; with 8 lanes per environment a wave holds 8 environments: ONE block whose
     // columns 8..15 are padding (zero observations in, outputs never read -- GEMM columns do not mix)
     static constexpr int NB = (16 * LANES >= WAVE) ? 1 : WAVE / (16 * LANES);
@@ -1397,7 +1353,7 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
     using R = Record<E>;
     const int rf = cx.count ? RecordCompact<E>::F : R::F;          // floats per record: compact or full format
     constexpr bool MFMA = MlpPath<T, E, LANES, H>::MFMA;
-    static_assert(LANES <= 4 || MFMA || (ATACOM_MLP8_VALU && std::is_same<T, float>::value), "8 lanes per environment: float32 only");
+    static_assert(LANES <= 4 || MFMA, "8 lanes per environment: float32 only");
     constexpr int THREADS = MlpPath<T, E, LANES, H>::THREADS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     T* lds = reinterpret_cast<T*>(smem);
@@ -1472,10 +1428,7 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
         // (one environment per lane with the network's four GEMM blocks live is the one kernel at the edge of the register
         // file: with the G(0) hoist its spills move INTO the sub-step loop -- 59.6 -> 79.5 us per step, measured -- so it
         // keeps the un-hoisted solver)
-#ifndef ATACOM_MLP_PARK
-#define ATACOM_MLP_PARK 1           // -DATACOM_MLP_PARK=0: the build that shows the defect described at env_step (PARKDYN)
-#endif
-        env_step<T, E, LANES, HOLD, DYN, (LANES > 1), CHART, THREADS, /*PARKDYN*/ DYN && ATACOM_MLP_PARK>(P, st, act, out, lq, ref);
+        env_step<T, E, LANES, HOLD, DYN, (LANES > 1), CHART, THREADS, /*PARKDYN*/ DYN>(P, st, act, out, lq, ref);
         if (lq == 0 && valid) {           // (shadow lanes of the MFMA path never append an exception row or write a tail)
             if (rec) {
                 if (!cx.count) {
@@ -1702,17 +1655,10 @@ __global__ void __launch_bounds__(WAVE) k_inverse_dynamics(int n, const T* __res
 #pragma unroll
     for (int i = 0; i < 9; ++i) { q9[i] = q[(size_t)b * 9 + i]; dq9[i] = dq[(size_t)b * 9 + i]; dd9[i] = ddq[(size_t)b * 9 + i]; }
     T Ml[9][9];
-#if ATACOM_DYN_LINK
     lk::Trig9<T> tg;
     lk::trig9(q9, tg);
     lk::rnea9(tg, dq9, dd9, t9);
     if (M) lk::crba<T, 9>(tg, Ml);
-#else
-    Chain9<T> ch;
-    iiwa_chain9(q9, ch);
-    rnea9(ch, dq9, dd9, t9);
-    if (M) crba<T, 9>(ch, Ml);
-#endif
 #pragma unroll
     for (int i = 0; i < 9; ++i) tau[(size_t)b * 9 + i] = t9[i];
     if (M) {
@@ -1735,17 +1681,10 @@ __global__ void __launch_bounds__(WAVE) k_forward_dynamics(int n, const T* __res
         dd9[i] = (i >= 6 && ddq_aux) ? ddq_aux[(size_t)b * 3 + (i >= 6 ? i - 6 : 0)] : T(0);
     }
     T rhs[6], Ml[6][6];
-#if ATACOM_DYN_LINK
     lk::Trig9<T> tg;
     lk::trig9(q9, tg);
     lk::rnea9(tg, dq9, dd9, bias);
     lk::crba<T, 6>(tg, Ml);
-#else
-    Chain9<T> ch;
-    iiwa_chain9(q9, ch);
-    rnea9(ch, dq9, dd9, bias);
-    crba<T, 6>(ch, Ml);
-#endif
 #pragma unroll
     for (int i = 0; i < 6; ++i)
         rhs[i] = tau6[(size_t)b * 6 + i] - bias[i] - (use_damping ? (T)iiwa_body::DAMPING[i] * dq9[i] : T(0));

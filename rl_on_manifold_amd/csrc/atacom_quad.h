@@ -263,9 +263,6 @@ __device__ __forceinline__ void split_sum(double (&h)[H2]) {
         h[H + k] = dpp_mov<DPP_ROW_HALF_MIRROR>(x);
     }
 }
-#ifndef ATACOM_P_RELABEL
-#define ATACOM_P_RELABEL 1          // -DATACOM_P_RELABEL=0: the A/B build with the butterfly sums in the P-application
-#endif
 
 template <int O, int LN = 4, typename T> __device__ __forceinline__ vec2<T> qbcast2(vec2<T> v) {
     return vec2<T>{qbcast<O, LN>(v.x), qbcast<O, LN>(v.y)};
@@ -458,7 +455,7 @@ __device__ __forceinline__ void bidiag_solve_null_quad_inl(AF&& aget, A0F&& a0ge
     // RELABEL (8 lanes, K + 1 even): the upper half of the group holds vector (q + H) mod 2H in physical slot q (split_sum)
     // (K + 1 = 6, the iiwa shape, only: with four vectors the split form is 11 instructions with their wait states against the
     // butterfly's 12 and a longer dependent chain -- the planar T-step kernel measured 8.8 instead of 8.3 us per step)
-    constexpr bool RELABEL = ATACOM_P_RELABEL && LN == 8 && K + 1 == 6;
+    constexpr bool RELABEL = LN == 8 && K + 1 == 6;
     constexpr int HV = (K + 1) / 2;
     const bool hf = RELABEL && (lq >= LN / 2);
     V2 nx[S][KP], nx0[KP];

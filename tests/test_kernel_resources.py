@@ -66,9 +66,10 @@ def test_no_promoted_arrays_and_no_scratch_in_the_production_kernels(tmp_path):
                  'k_rollout_mlp<double, Iiwa, 2, true, 64, false, 0, false>', 'k_rollout_mlp<double, Iiwa, 4, true, 64, false, 1, false>'):
         assert gone not in names, gone
     assert any(k[0].startswith('k_step<float, Iiwa, 4, true, false, 0, false>') for k in ks), [k[0] for k in ks][:5]
-    # static LDS: the two-stage statistics reduction, and the float32 rigid-body kernels of the reference chart, which park
+    # static LDS: the two-stage statistics reduction, and the float32 rigid-body kernels of the reference chart, which may park
     # the held solver state across the dynamics (84 values per lane: 21 float4 x threads per workgroup; atacom_kernels.h) --
-    # nothing else (the policy kernels' LDS is dynamic)
+    # nothing else (the policy kernels' network LDS is dynamic).  Of those only the policy kernels of the lane groups park
+    # (PARKDYN); the step / rollout kernels stopped in round 5, which parked() still admits
     def args(name):
         return [a.strip() for a in name[name.index('<') + 1:name.rindex('>')].split(',')]
 
@@ -92,8 +93,9 @@ def test_no_promoted_arrays_and_no_scratch_in_the_production_kernels(tmp_path):
         a = args(name)                                       # T, E, LANES, HOLD, DYN, CHART, NOISE
         if a[4] == 'true':
             # rigid-body mode (opt-in).  Quad mapping, reference chart, held q (the mode's default configuration):
-            # NO scratch since the solver state is parked in LDS across the dynamics (round 4; it had been 32 - 208 bytes per
-            # lane); the other instantiations (one environment per lane, refreshed q, canonical chart) are bounded
+            # NO scratch -- the link-coordinate dynamics (round 5) fit next to the held solver state without parking it; the
+            # world-coordinate form had spilled 32 - 208 bytes per lane -- the other instantiations (one environment per lane,
+            # refreshed q, canonical chart) are bounded
             if scratch > (0 if (a[2] == '4' and a[3] == 'true' and a[5] == '0') else 700):
                 bad.append((name, scratch))
             continue
@@ -102,7 +104,7 @@ def test_no_promoted_arrays_and_no_scratch_in_the_production_kernels(tmp_path):
         if noise and a[3] == 'false' and name.startswith('k_rollout<'):
             continue                                         # ... refreshed q (hold_q = 0) in a T-step kernel: two of them spill
         if noise and a[5] == '1' and a[1] == 'Planar' and scratch <= 32:
-            continue                                         # ... the planar canonical-chart step kernel (second form): 20 bytes
+            continue                                         # ... planar canonical chart (20 bytes in a retired form)
         if name.startswith('k_step<') or int(a[2]) > 1:
             if scratch:
                 bad.append((name, scratch))
