@@ -19,6 +19,7 @@
 #ifndef ATACOM_HIP_H
 #define ATACOM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -200,7 +201,8 @@ int atacom_rollout(atacom_handle* h, int32_t n_steps, const void* d_actions, voi
  * reference training script builds (examples/network.py:8-36,39-68,266-293: Linear(n_in,64)-ReLU-Linear(64,64)-ReLU-
  * Linear(64,n_out)); weights in torch.nn.Linear layout W[out][in], element type = the handle's dtype, device memory.
  * action = MLP((obs - obs_shift) * obs_scale) + std * noise   (MinMaxPreprocessor + GaussianTorchPolicy of
- * examples/iiwa_air_hockey_exp.py:32-34,138-146); d_noise [n_steps, batch, n_out] is supplied by the caller (NULL = 0). */
+ * examples/iiwa_air_hockey_exp.py:32-34,138-146); d_noise [n_steps, batch, n_out] is supplied by the caller (NULL = 0).
+ * SAC, TD3 and DDPG exploration: see squash / the sigma network and mean_mode / explore below. */
 typedef struct atacom_mlp {
     int32_t struct_size;  /* = sizeof(atacom_mlp) */
     int32_t n_in;         /* must equal obs_dim */
@@ -218,7 +220,29 @@ typedef struct atacom_mlp {
     double log_std_min, log_std_max;               /* MushroomRL's SACPolicy uses -20, 2 */
     int32_t squash;
     int32_t reserved1;
+    /* ---- fields below were appended after the first release of this struct.  A struct_size equal to
+     * ATACOM_MLP_SIZE_V1 (the size up to reserved1) is still accepted and runs mean_mode = explore = 0.
+     * TD3 / DDPG actors (examples/network.py:112-147 TD3ActorNetwork, :197-232 DDPGActorNetwork) squash the MEAN:
+     * mean = act_scale * tanh(h3(...)), and explore with noise that acts after the squash:
+     *   explore = 1, clipped Gaussian (MushroomRL ClippedGaussianPolicy, TD3):  a = clip(mean + std * eps, act_low, act_high);
+     *   explore = 2, Ornstein-Uhlenbeck (MushroomRL OrnsteinUhlenbeckPolicy, DDPG), per environment:
+     *       x <- x - ou_theta * x * ou_dt + std * sqrt(ou_dt) * eps;   a = mean + x   (recorded unclipped).
+     *     x lives in ou_state between calls.  Before the draw of any step at which an environment's episode step counter
+     *     is 0 -- after an explicit, masked or automatic reset -- its x is set to ou_x0 (MushroomRL's policy.reset() at
+     *     episode start).  ou_state is the caller's: a snapshot does not contain it.
+     * explore != 0 excludes squash and the sigma network; mean_mode = 1 combines with every explore mode.  All of these
+     * are launch-uniform options of the same kernels. */
+    int32_t mean_mode;                 /* 0: mean = h3(...);  1: mean = act_scale * tanh(h3(...)) */
+    int32_t explore;                   /* 0: Gaussian (squash / sigma network apply), 1: clipped Gaussian, 2: OU */
+    const void *act_scale;             /* [n_out], NULL = 1 */
+    const void *act_low, *act_high;    /* [n_out], required by explore = 1 */
+    double ou_theta, ou_dt;            /* explore = 2; ou_dt > 0 */
+    const void *ou_x0;                 /* [n_out], NULL = zeros: the value x takes at every episode start */
+    void *ou_state;                    /* [batch, n_out] of the handle's dtype, in / out, device memory; explore = 2 */
 } atacom_mlp;
+
+/* sizeof(atacom_mlp) before mean_mode was appended: C callers built against that header keep working */
+#define ATACOM_MLP_SIZE_V1 ((int32_t)offsetof(atacom_mlp, mean_mode))
 
 /* Like atacom_rollout, with d_actions [n_steps, batch, n_out] an OUTPUT (the actions the policy drew). */
 int atacom_rollout_mlp(atacom_handle* h, int32_t n_steps, const atacom_mlp* net, const void* d_noise, void* d_obs,

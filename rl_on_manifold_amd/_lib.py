@@ -46,7 +46,15 @@ class AtacomMlp(C.Structure):
                 ('std', C.c_void_p),
                 ('sW1', C.c_void_p), ('sb1', C.c_void_p), ('sW2', C.c_void_p), ('sb2', C.c_void_p),
                 ('sW3', C.c_void_p), ('sb3', C.c_void_p), ('log_std_min', C.c_double), ('log_std_max', C.c_double),
-                ('squash', C.c_int32), ('reserved1', C.c_int32)]
+                ('squash', C.c_int32), ('reserved1', C.c_int32),
+                # appended (TD3 / DDPG): a struct_size of MLP_SIZE_V1 still selects the first release's layout
+                ('mean_mode', C.c_int32), ('explore', C.c_int32), ('act_scale', C.c_void_p), ('act_low', C.c_void_p),
+                ('act_high', C.c_void_p), ('ou_theta', C.c_double), ('ou_dt', C.c_double), ('ou_x0', C.c_void_p),
+                ('ou_state', C.c_void_p)]
+
+
+MLP_SIZE_V1 = AtacomMlp.mean_mode.offset          # ATACOM_MLP_SIZE_V1
+EXPLORE_GAUSSIAN, EXPLORE_CLIPPED, EXPLORE_OU = 0, 1, 2
 
 
 class AtacomDims(C.Structure):

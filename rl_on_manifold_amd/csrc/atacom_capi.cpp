@@ -153,7 +153,7 @@ void default_init_row(int env_id, int task, std::vector<double>& row) {
 }  // namespace
 
 struct atacom_handle;
-static int check_mlp(const atacom_handle* h, const atacom_mlp* net, const char* who);
+static int check_mlp(const atacom_handle* h, const atacom_mlp* in, const char* who, atacom_mlp* net);
 
 struct atacom_handle {
     atacom_config cfg;
@@ -312,10 +312,14 @@ static hipError_t calibrate_step_lanes(atacom_handle* h) {
     return e;
 }
 
-static int check_mlp(const atacom_handle* h, const atacom_mlp* net, const char* who) {
+// Validates *in and copies it to *net: a struct of the first release's size (ATACOM_MLP_SIZE_V1) gets the appended fields
+// zeroed (mean_mode = explore = 0, what it ran before they existed); its memory past that size is never read.
+static int check_mlp(const atacom_handle* h, const atacom_mlp* in, const char* who, atacom_mlp* net) {
     const std::string w(who);
-    if (net->struct_size != (int32_t)sizeof(atacom_mlp))
+    if (in->struct_size != (int32_t)sizeof(atacom_mlp) && in->struct_size != ATACOM_MLP_SIZE_V1)
         return fail(ATACOM_E_INVALID, w + ": atacom_mlp.struct_size mismatch (ABI)");
+    std::memset(net, 0, sizeof(atacom_mlp));
+    std::memcpy(net, in, (size_t)in->struct_size);
     if (net->n_in != h->ops->obs_dim || net->n_out != h->ops->nk)
         return fail(ATACOM_E_INVALID, w + ": network n_in / n_out must equal obs_dim / n_null");
     if (!net->W1 || !net->b1 || !net->W2 || !net->b2 || !net->W3 || !net->b3)
@@ -326,6 +330,18 @@ static int check_mlp(const atacom_handle* h, const atacom_mlp* net, const char* 
         return fail(ATACOM_E_INVALID, w + ": the sigma network needs all six weight pointers (or none)");
     if (net->activation != 0 && net->activation != 1)
         return fail(ATACOM_E_INVALID, w + ": activation must be 0 (ReLU) or 1 (tanh)");
+    if (net->mean_mode != 0 && net->mean_mode != 1)
+        return fail(ATACOM_E_INVALID, w + ": mean_mode must be 0 (linear) or 1 (act_scale * tanh)");
+    if (net->explore < 0 || net->explore > 2)
+        return fail(ATACOM_E_INVALID, w + ": explore must be 0 (Gaussian), 1 (clipped Gaussian) or 2 (Ornstein-Uhlenbeck)");
+    if (net->explore != 0 && (net->squash || n_sig != 0))
+        return fail(ATACOM_E_INVALID, w + ": explore = 1 / 2 does not combine with squash or a sigma network");
+    if (net->explore == 1 && (!net->act_low || !net->act_high))
+        return fail(ATACOM_E_INVALID, w + ": explore = 1 (clipped Gaussian) needs act_low and act_high");
+    if (net->explore == 2 && !net->ou_state)
+        return fail(ATACOM_E_INVALID, w + ": explore = 2 (Ornstein-Uhlenbeck) needs ou_state");
+    if (net->explore == 2 && !(net->ou_dt > 0.0))
+        return fail(ATACOM_E_INVALID, w + ": explore = 2 (Ornstein-Uhlenbeck) needs ou_dt > 0");
     return ATACOM_OK;
 }
 
@@ -560,12 +576,13 @@ int atacom_rollout_mlp(atacom_handle* h, int32_t n_steps, const atacom_mlp* net,
                        void* stream) {
     if (!h || !net) return fail(ATACOM_E_INVALID, "atacom_rollout_mlp: null handle / network");
     if (n_steps <= 0) return fail(ATACOM_E_INVALID, "atacom_rollout_mlp: n_steps must be positive");
-    const int vrc = check_mlp(h, net, "atacom_rollout_mlp");
+    atacom_mlp m;
+    const int vrc = check_mlp(h, net, "atacom_rollout_mlp", &m);
     if (vrc != ATACOM_OK) return vrc;
     if (!d_obs || !d_actions || !d_reward || !d_absorbing || !d_last)
         return fail(ATACOM_E_INVALID, "atacom_rollout_mlp: all output buffers except d_next_obs are required");
     ON_DEVICE(h);
-    const int rc = stepper(h).rollout_mlp(h->cfg, policy_lanes(h), n_steps, *net, h->f, h->ip, d_noise, d_obs,
+    const int rc = stepper(h).rollout_mlp(h->cfg, policy_lanes(h), n_steps, m, h->f, h->ip, d_noise, d_obs,
                                        d_next_obs, d_actions, d_reward, d_absorbing, d_last, nullptr, 0, nullptr,
                                        (hipStream_t)stream);
     if (rc != ATACOM_OK)
@@ -594,8 +611,9 @@ static int rollout_records(atacom_handle* h, const char* fn, int32_t n_steps, co
         if (cx->cap < 0 || (cx->cap > 0 && !cx->ends))
             return fail(ATACOM_E_INVALID, name + ": ends_capacity must be >= 0, and d_ends given when it is positive");
     }
+    atacom_mlp m{};
     if (net) {
-        const int vrc = check_mlp(h, net, fn);
+        const int vrc = check_mlp(h, net, fn, &m);
         if (vrc != ATACOM_OK) return vrc;
     }
     ON_DEVICE(h);
@@ -604,7 +622,7 @@ static int rollout_records(atacom_handle* h, const char* fn, int32_t n_steps, co
         stepper(h).rollout(h->cfg, rollout_lanes(h), n_steps, h->f, h->ip, d_actions, nullptr, nullptr, nullptr,
                            nullptr, nullptr, d_records, record_batch_stride, cx, (hipStream_t)stream);
     } else {
-        const int rc = stepper(h).rollout_mlp(h->cfg, policy_lanes(h), n_steps, *net, h->f, h->ip, d_noise, nullptr,
+        const int rc = stepper(h).rollout_mlp(h->cfg, policy_lanes(h), n_steps, m, h->f, h->ip, d_noise, nullptr,
                                               nullptr, nullptr, nullptr, nullptr, nullptr, d_records, record_batch_stride, cx,
                                               (hipStream_t)stream);
         if (rc != ATACOM_OK)

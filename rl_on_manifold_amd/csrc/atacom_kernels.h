@@ -1319,7 +1319,7 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_rollout(const Params<T> P, int
 }
 
 // Row N2: rollout with the policy MLP evaluated in the kernel (atacom_policy.h).  d_actions_out receives the action
-// the policy drew (mean + std * noise, before the env's clip to [-1, 1]).
+// the policy drew (mean + std * noise, before the env's clip to [-1, 1]; TD3: clipped to [act_low, act_high]; DDPG: mean + x).
 // float: the network runs on the matrix cores (mlp_forward_mfma), one wavefront = 1 (quad mapping) or 4 (lane mapping)
 // GEMM column blocks of 16 environments.  Every lane of a live wave must then stay in the kernel (it supplies operand
 // slices for ALL environments of its blocks), so lanes past the end of the batch shadow the last environment with
@@ -1389,6 +1389,28 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
         for (int k = 0; k < E::NK; ++k) eps[k] = noise ? noise[row * E::NK + k] : T(0);
         T o[E::OBS];
         write_obs<T, E>(P, st, o, ref);
+        // [act_scale | act_low | act_high | x0 | std sqrt(dt)] of the TD3 / DDPG modes (mlp_stage_explore)
+        const T* const xc = lds + (MFMA ? (int)LM::EXPLORE : (int)MlpLds<E::OBS, H, E::NK>::EXPLORE);
+        if (net.explore == 2) {
+            // DDPG's Ornstein-Uhlenbeck process, advanced BEFORE the network and carried through it in the registers of eps
+            // (nothing is added to what the network and the solver hold): restarted at x0 at every episode start (st.t == 0:
+            // explicit, masked or automatic reset alike), then x <- x - theta dt x + std sqrt(dt) eps.  x is read every
+            // step -- what the committing lane stored the step before -- not carried across the solver; its address is
+            // formed anew each step (hoisted out of the loop it held two registers through the solver).  The draw below
+            // then runs with std = 0 (staged so) and x is added after it: mean + x, recorded unclipped.
+            int bx = b;
+            asm volatile("" : "+v"(bx));
+            T* const xp = net.ou_state + (size_t)bx * E::NK;
+#pragma unroll
+            for (int k = 0; k < E::NK; ++k) {
+                const T x = st.t == 0 ? xc[24 + k] : xp[k];
+                eps[k] = num<T>::fma(xc[32 + k], eps[k], x - net.ou_theta_dt * x);
+            }
+            if (lq == 0 && valid) {
+#pragma unroll
+                for (int k = 0; k < E::NK; ++k) xp[k] = eps[k];
+            }
+        }
         T act[E::NK], sig[E::NK];
         if constexpr (MFMA) {
             float xin[NB][LM::CH];
@@ -1410,10 +1432,24 @@ __global__ void __launch_bounds__(256) k_rollout_mlp(const Params<T> P, const Ml
 #pragma unroll
             for (int k = 0; k < E::NK; ++k) sig[k] = lds[(MFMA ? (int)LM::STD : (int)MlpLds<E::OBS, H, E::NK>::STD) + k];
         }
+        if (net.mean_mode) {
+            // TD3 / DDPG actors: the mean itself is squashed and scaled (examples/network.py:144-146,229-231)
+#pragma unroll
+            for (int k = 0; k < E::NK; ++k) act[k] = xc[k] * num<T>::tanh(act[k]);
+        }
+        // (explore = 2: std = 0, this leaves the mean; eps = the process's new x)
 #pragma unroll
         for (int k = 0; k < E::NK; ++k) {
             act[k] = num<T>::fma(sig[k], eps[k], act[k]);
             if (net.squash) act[k] = num<T>::tanh(act[k]);
+        }
+        if (net.explore == 1) {
+            // TD3's clipped Gaussian; the action recorded is the clipped one
+#pragma unroll
+            for (int k = 0; k < E::NK; ++k) act[k] = num<T>::clamp(act[k], xc[8 + k], xc[16 + k]);
+        } else if (net.explore == 2) {
+#pragma unroll
+            for (int k = 0; k < E::NK; ++k) act[k] += eps[k];
         }
         T* const rrow = rec ? rec + ((size_t)t * rec_ld + b) * rf : nullptr;
         if (lq == 0 && valid) {

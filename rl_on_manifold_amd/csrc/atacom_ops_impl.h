@@ -145,6 +145,11 @@ struct Variant {
         a.sW3 = (const T*)net.sW3; a.sb3 = (const T*)net.sb3;
         a.log_std_min = (T)net.log_std_min; a.log_std_max = (T)net.log_std_max; a.squash = net.squash;
         a.n_in = net.n_in; a.n_out = net.n_out; a.activation = net.activation;
+        a.mean_mode = net.mean_mode; a.explore = net.explore;
+        a.act_scale = (const T*)net.act_scale; a.act_low = (const T*)net.act_low; a.act_high = (const T*)net.act_high;
+        a.ou_x0 = (const T*)net.ou_x0; a.ou_state = (T*)net.ou_state;
+        // x <- x - (theta dt) x + (sqrt(dt) std) eps: the two products of constants formed once, in double
+        a.ou_theta_dt = (T)(net.ou_theta * net.ou_dt); a.ou_sqrt_dt = (T)(net.explore == 2 ? std::sqrt(net.ou_dt) : 0.0);
         if constexpr (E::ID != 0) {
             // float64 (the parity build): the policy kernel exists for the default variant only -- reference chart, kinematic,
             // no domain randomisation -- which is what the 1e-8 parity tests of row N2 run (tests/test_gpu_parity.py)

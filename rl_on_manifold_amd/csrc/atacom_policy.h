@@ -32,7 +32,30 @@ struct MlpArgs {
     T log_std_min, log_std_max;              // clamp of the sigma network's output (MushroomRL SACPolicy: -20, 2)
     int n_in, n_out, activation;             // activation: 0 ReLU, 1 tanh
     int squash;                              // 1: action = tanh(mean + sigma * eps)   (SAC's squashed Gaussian)
+    // TD3 / DDPG actors (include/atacom_hip.h: atacom_mlp.mean_mode, .explore); launch-uniform, all of it after the network
+    int mean_mode;                           // 1: mean = act_scale * tanh(mean)
+    int explore;                             // 0 Gaussian, 1 clip(mean + std eps, low, high), 2 Ornstein-Uhlenbeck
+    const T *act_scale, *act_low, *act_high; // staged into LDS with the network (nullable: 1 / unused)
+    const T *ou_x0;                          // OU state at every episode start (nullable: 0)
+    T* ou_state;                             // [batch, n_out]: read every step, written by the committing lane
+    T ou_theta_dt, ou_sqrt_dt;               // theta * dt and sqrt(dt), formed on the host
 };
+
+// The per-action constants of the TD3 / DDPG modes, staged next to STD in both LDS layouts:
+// [act_scale | low | high | x0 | std sqrt(dt)].  The Ornstein-Uhlenbeck mode applies its std through the last one (to eps,
+// before the network) and stages std = 0: the Gaussian draw mean + std eps then leaves the mean, and x is added after it.
+template <typename T>
+__device__ __forceinline__ void mlp_stage_explore(const MlpArgs<T>& net, T* dst, T* std, int tid, int nthreads) {
+    for (int i = tid; i < 8; i += nthreads) {
+        const bool real = i < net.n_out;
+        dst[i] = (real && net.act_scale) ? net.act_scale[i] : T(1);
+        dst[8 + i] = (real && net.act_low) ? net.act_low[i] : T(0);
+        dst[16 + i] = (real && net.act_high) ? net.act_high[i] : T(0);
+        dst[24 + i] = (real && net.ou_x0) ? net.ou_x0[i] : T(0);
+        dst[32 + i] = (real && net.std && net.explore == 2) ? net.std[i] * net.ou_sqrt_dt : T(0);
+        if (net.explore == 2) std[i] = T(0);
+    }
+}
 
 template <int D, int H, int NK>
 struct MlpLds {
@@ -41,7 +64,7 @@ struct MlpLds {
     static constexpr int S3 = 8;                        // W3 stored transposed: [unit][out], NK <= 8
     static constexpr int W1 = 0, W2 = W1 + H * S1, W3T = W2 + H * S2, B1 = W3T + H * S3, B2 = B1 + H,
                          B3 = B2 + H, SHIFT = B3 + 8, SCALE = SHIFT + ((D + 3) / 4) * 4,
-                         STD = SCALE + ((D + 3) / 4) * 4, TOTAL = STD + 8;
+                         STD = SCALE + ((D + 3) / 4) * 4, EXPLORE = STD + 8, TOTAL = EXPLORE + 40;
 };
 
 // cooperative staging by the whole workgroup (call before any early return)
@@ -67,6 +90,8 @@ __device__ __forceinline__ void mlp_stage(const MlpArgs<T>& net, T* lds, int tid
     if (net.sW1)
         mlp_stage_weights<T, D, H, NK>(lds + L::TOTAL, net.sW1, net.sb1, net.sW2, net.sb2, net.sW3, net.sb3, tid, nthreads);
     for (int i = tid; i < NK; i += nthreads) lds[L::STD + i] = net.std ? net.std[i] : T(0);
+    __syncthreads();
+    mlp_stage_explore<T>(net, lds + L::EXPLORE, lds + L::STD, tid, nthreads);
     for (int i = tid; i < D; i += nthreads) {
         lds[L::SHIFT + i] = net.obs_shift ? net.obs_shift[i] : T(0);
         lds[L::SCALE + i] = net.obs_scale ? net.obs_scale[i] : T(1);
@@ -196,7 +221,7 @@ struct MlpLdsM {
     static constexpr int S1 = 32;                // W1 row: [lane group g][8] holding elements CH g + s
     static constexpr int S2 = H + 4;             // W2 / W3 rows (k contiguous), padded against bank conflicts
     static constexpr int W1 = 0, W2 = W1 + H * S1, W3 = W2 + H * S2, B1 = W3 + 16 * S2, B2 = B1 + H, B3 = B2 + H,
-                         SHIFT = B3 + 16, SCALE = SHIFT + 32, STD = SCALE + 32, NET = STD + 16;
+                         SHIFT = B3 + 16, SCALE = SHIFT + 32, STD = SCALE + 32, EXPLORE = STD + 16, NET = EXPLORE + 40;
     // per-wave staging (floats) for NB blocks of 16 environments: observations [env][32], action means [env][8]
     static constexpr int XT = 0;
     static constexpr int act_offset(int nb) { return 16 * nb * 32; }
@@ -230,6 +255,8 @@ __device__ __forceinline__ void mlp_stage_mfma(const MlpArgs<float>& net, float*
     if (net.sW1)
         mlp_stage_weights_mfma<D, H, NK>(lds + L::NET, net.sW1, net.sb1, net.sW2, net.sb2, net.sW3, net.sb3, tid, nthreads);
     for (int i = tid; i < NK; i += nthreads) lds[L::STD + i] = net.std ? net.std[i] : 0.0f;
+    __syncthreads();
+    mlp_stage_explore<float>(net, lds + L::EXPLORE, lds + L::STD, tid, nthreads);
     for (int i = tid; i < 32; i += nthreads) {
         // [g][8] like W1; padding: shift 0, scale 1 (the padded observation elements are 0)
         const int g = i / 8, s = i % 8, e = L::CH * g + s;

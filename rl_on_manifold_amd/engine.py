@@ -589,7 +589,10 @@ class MlpPolicy:
 
     `MlpPolicy.from_module(net)` accepts any module with `_h1/_h2/_h3` nn.Linear layers -- exactly the attribute
     names of the reference's PPONetwork / TRPONetwork / SACActorNetwork (examples/network.py:19-21,50-52,277-279).
-    obs_low / obs_high give the MinMaxPreprocessor normalisation x = (obs - mean) / delta of the finite bounds."""
+    obs_low / obs_high give the MinMaxPreprocessor normalisation x = (obs - mean) / delta of the finite bounds.
+    `from_td3` / `from_ddpg` take the reference's TD3ActorNetwork / DDPGActorNetwork (mean = action_scaling * tanh(h3))
+    with their exploration: TD3's clipped Gaussian, DDPG's Ornstein-Uhlenbeck process, whose per-environment state the
+    policy owns (`noise_state`)."""
 
     def __init__(self, W1, b1, W2, b2, W3, b3, std=None, obs_shift=None, obs_scale=None, activation='relu',
                  sigma_weights=None, squash=False, log_std_min=-20.0, log_std_max=2.0):
@@ -598,7 +601,97 @@ class MlpPolicy:
             self.tensors.update(dict(zip(('sW1', 'sb1', 'sW2', 'sb2', 'sW3', 'sb3'), sigma_weights)))
         self.activation = {'relu': 0, 'tanh': 1}[activation]
         self.squash, self.log_std_min, self.log_std_max = bool(squash), float(log_std_min), float(log_std_max)
+        self.mean_mode, self.explore = 0, _lib.EXPLORE_GAUSSIAN
+        self.ou_theta, self.ou_dt = 0.0, 0.0
+        self.noise_state = None                            # [batch, n_out] OU state (from_ddpg), allocated by as_struct
         self._keep = None
+
+    def _n_out(self):
+        return int(torch.as_tensor(self.tensors['W3']).shape[0])
+
+    def _vec(self, v, what):
+        """A scalar or an [n_out] vector -> [n_out] float64 tensor."""
+        k = self._n_out()
+        t = torch.as_tensor(v, dtype=torch.float64).detach().cpu().reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(k)
+        if t.numel() != k:
+            raise ValueError("%s: expected a scalar or %d values, got %d" % (what, k, t.numel()))
+        return t.clone()
+
+    def _scaled_mean(self, actor):
+        self.mean_mode = 1
+        self.tensors['act_scale'] = self._vec(getattr(actor, '_action_scaling', 1.0), 'action_scaling')
+
+    @classmethod
+    def from_td3(cls, actor, sigma, low=-1.0, high=1.0, obs_low=None, obs_high=None):
+        """TD3's exploration policy (MushroomRL ClippedGaussianPolicy as examples/iiwa_air_hockey_exp.py:256-263 builds it):
+        action = clip(mu(obs) + std * eps, low, high) with mu = actor._action_scaling * tanh(h3(...)) (TD3ActorNetwork).
+        `sigma` is the COVARIANCE the reference passes (np.eye(k) * sigma): a matrix, or a scalar meaning eye(k) * sigma;
+        std = sqrt(diag(sigma)).  Only diagonal covariances are supported."""
+        pol = cls.from_module(actor, obs_low=obs_low, obs_high=obs_high)
+        k = pol._n_out()
+        S = torch.as_tensor(sigma, dtype=torch.float64).detach().cpu()
+        if S.dim() == 0 or S.numel() == 1:
+            S = torch.eye(k, dtype=torch.float64) * S.reshape(())
+        if tuple(S.shape) != (k, k):
+            raise ValueError("from_td3: sigma must be a scalar or a [%d, %d] covariance matrix" % (k, k))
+        if bool((S - torch.diag(torch.diagonal(S))).abs().max() > 0):
+            raise ValueError("from_td3: only diagonal covariances are supported")
+        d = torch.diagonal(S)
+        if bool((d < 0).any()):
+            raise ValueError("from_td3: the covariance has a negative diagonal entry")
+        pol._scaled_mean(actor)
+        pol.tensors['std'] = d.sqrt()
+        pol.tensors['act_low'], pol.tensors['act_high'] = pol._vec(low, 'low'), pol._vec(high, 'high')
+        if bool((pol.tensors['act_low'] > pol.tensors['act_high']).any()):
+            raise ValueError("from_td3: low must not exceed high")
+        pol.explore = _lib.EXPLORE_CLIPPED
+        return pol
+
+    @classmethod
+    def from_ddpg(cls, actor, sigma, theta, dt, x0=None, obs_low=None, obs_high=None):
+        """DDPG's exploration policy (MushroomRL OrnsteinUhlenbeckPolicy as examples/iiwa_air_hockey_exp.py:213-217 builds
+        it): per environment x <- x - theta x dt + sigma sqrt(dt) eps, action = mu(obs) + x with mu = actor._action_scaling *
+        tanh(h3(...)) (DDPGActorNetwork).  x restarts at x0 (None = zeros) at every episode start.  The policy owns x:
+        `noise_state` [batch, n_out], allocated as zeros by the first call with an env and bound to that env's batch,
+        device and dtype from then on; `reset_noise()` sets it to x0."""
+        if not float(dt) > 0.0:
+            raise ValueError("from_ddpg: dt must be positive")
+        pol = cls.from_module(actor, obs_low=obs_low, obs_high=obs_high)
+        pol._scaled_mean(actor)
+        pol.tensors['std'] = pol._vec(sigma, 'sigma')
+        if x0 is not None:
+            pol.tensors['ou_x0'] = pol._vec(x0, 'x0')
+        pol.explore, pol.ou_theta, pol.ou_dt = _lib.EXPLORE_OU, float(theta), float(dt)
+        return pol
+
+    def reset_noise(self, mask=None):
+        """OrnsteinUhlenbeckPolicy.reset() for the environments selected by `mask` ([batch] bool, None = all): their noise
+        state becomes x0.  (The rollout kernels do this by themselves at every episode start.)"""
+        if self.noise_state is None:
+            return
+        x0 = self.tensors.get('ou_x0')
+        x0 = torch.zeros(self._n_out(), dtype=torch.float64) if x0 is None else torch.as_tensor(x0)
+        x0 = x0.to(device=self.noise_state.device, dtype=self.noise_state.dtype)
+        if mask is None:
+            self.noise_state.copy_(x0.expand_as(self.noise_state))
+        else:
+            m = torch.as_tensor(mask, device=self.noise_state.device).reshape(-1).bool()
+            if m.numel() != self.noise_state.shape[0]:
+                raise ValueError("reset_noise: mask must have %d entries" % self.noise_state.shape[0])
+            self.noise_state[m] = x0
+
+    def _ou_state_for(self, env):
+        shape = (env.batch, self._n_out())
+        if self.noise_state is None:
+            self.noise_state = torch.zeros(shape, device=env.device, dtype=env.dtype)
+        ns = self.noise_state
+        if tuple(ns.shape) != shape or ns.dtype != env.dtype or not env._on_my_device(ns) or not ns.is_contiguous():
+            raise ValueError("this policy's noise state is a %s %s tensor on %s; the env needs [%d, %d] %s on %s "
+                             "(one DDPG policy per env shard)" % (tuple(ns.shape), ns.dtype, ns.device, env.batch,
+                                                                  shape[1], env.dtype, env.device))
+        return ns
 
     @classmethod
     def from_sac(cls, mu_net, sigma_net, obs_low=None, obs_high=None, log_std_min=-20.0, log_std_max=2.0):
@@ -636,10 +729,14 @@ class MlpPolicy:
             raise ValueError("expected Linear(n_in,h) - Linear(h,h) - Linear(h,n_out)")
         m.activation = self.activation
         for k in ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'obs_shift', 'obs_scale', 'std', 'sW1', 'sb1', 'sW2', 'sb2',
-                  'sW3', 'sb3'):
+                  'sW3', 'sb3', 'act_scale', 'act_low', 'act_high', 'ou_x0'):
             v = dev.get(k)
             setattr(m, k, None if v is None else v.data_ptr())
         m.squash, m.log_std_min, m.log_std_max = int(self.squash), self.log_std_min, self.log_std_max
+        m.mean_mode, m.explore = self.mean_mode, self.explore
+        if self.explore == _lib.EXPLORE_OU:
+            m.ou_theta, m.ou_dt = self.ou_theta, self.ou_dt
+            m.ou_state = self._ou_state_for(env).data_ptr()
         return m
 
 
