@@ -21,4 +21,7 @@ def __getattr__(name):
     if name in ('RolloutCollector', 'RecordLayout', 'CompactRecordLayout'):
         from . import rollout
         return getattr(rollout, name)
+    if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
+        from . import point
+        return getattr(point, name)
     raise AttributeError(name)

@@ -1,4 +1,4 @@
-"""Build libatacom_hip.so in-tree with hipcc for gfx950 (no GPU needed: hipcc cross-compiles).
+"""Build libatacom_hip.so and libatacom_point.so in-tree with hipcc for gfx950 (no GPU needed: hipcc cross-compiles).
 
     python -m rl_on_manifold_amd.build [--force]
 
@@ -29,17 +29,38 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp']}
 
 
+# The collision-avoidance task (PointReachAtacom) is a library of its own, libatacom_point.so (include/atacom_point_hip.h):
+# its kernels stay out of the main library's census and it shares only headers (the solver of atacom_linalg.h) with it.
+LIB_POINT = os.environ.get('ATACOM_POINT_LIB_OUT') or os.path.join(HERE, 'libatacom_point.so')
+UNITS_POINT = ['atacom_point.hip', 'atacom_point_capi.cpp']
+_POINT_ONLY = ('atacom_point.hip', 'atacom_point_capi.cpp', 'atacom_point.h', 'atacom_point_ops.h')
+
+
 def _sources():
-    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
+    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in _POINT_ONLY]
     out.append(os.path.join(os.path.dirname(HERE), 'include', 'atacom_hip.h'))
     return out
 
 
-def needs_build():
-    if not os.path.exists(LIB):
+def _sources_point():
+    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h') or f in _POINT_ONLY]
+    out.append(os.path.join(os.path.dirname(HERE), 'include', 'atacom_point_hip.h'))
+    return out
+
+
+def _stale(lib, sources):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(p) > t for p in _sources())
+    t = os.path.getmtime(lib)
+    return any(os.path.getmtime(p) > t for p in sources)
+
+
+def needs_build():
+    return _stale(LIB, _sources())
+
+
+def needs_build_point():
+    return _stale(LIB_POINT, _sources_point())
 
 
 # kernel-tuning builds: ATACOM_KEEP_OBJ=1 keeps the objects of a build; ATACOM_ONLY_UNITS=a.hip,b.hip then recompiles only
@@ -51,7 +72,7 @@ def _compile(unit):
     src = os.path.join(CSRC, unit)
     tag = os.environ.get('ATACOM_OBJ_TAG', '')
     obj = os.path.join(CSRC, os.path.splitext(unit)[0] + tag + '.o')
-    if ONLY and unit not in ONLY:
+    if ONLY and unit in UNITS and unit not in ONLY:
         kept = os.path.join(CSRC, os.path.splitext(unit)[0] + os.environ.get('ATACOM_BASE_TAG', '_keep') + '.o')
         if not os.path.exists(kept):
             raise RuntimeError('ATACOM_ONLY_UNITS needs the kept object %s (build once with ATACOM_KEEP_OBJ=1 ATACOM_OBJ_TAG=_keep)' % kept)
@@ -100,6 +121,26 @@ def build(force=False, verbose=True):
     return LIB
 
 
+def build_point(force=False, verbose=True):
+    """libatacom_point.so: the second target (two units, a few seconds)."""
+    if not force and not needs_build_point():
+        return LIB_POINT
+    if verbose:
+        print('[atacom] building %s for %s ...' % (os.path.basename(LIB_POINT), ARCH), flush=True)
+    with ThreadPoolExecutor(max_workers=len(UNITS_POINT)) as ex:
+        objs = list(ex.map(_compile, UNITS_POINT))
+    cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB_POINT] + objs
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError('link failed:\n%s\n%s' % (' '.join(cmd), r.stderr[-4000:]))
+    if not os.environ.get('ATACOM_KEEP_OBJ'):
+        for o in objs:
+            os.remove(o)
+    return LIB_POINT
+
+
 if __name__ == '__main__':
     build(force='--force' in sys.argv)
+    build_point(force='--force' in sys.argv)
     print(LIB)
+    print(LIB_POINT)

@@ -1,0 +1,239 @@
+"""The collision-avoidance task (the reference's PointReachAtacom,
+atacom/environments/collision_avoidance/collision_avoidance_atacom.py:8) on libatacom_point.so.
+
+  BatchedPointReachEnv   B environments on one device, torch tensors in and out, the surface of BatchedAtacomEnv
+  PointReachAtacom       batch-1 numpy facade with the reference's constructor, argument for argument
+
+All arithmetic happens in the library (hand-written HIP, gfx950); this file only moves pointers.
+
+Random numbers.  The reference draws the obstacles' reset positions and random-walk accelerations from numpy's global
+generator.  Here a call either receives the draws (`draws=`, the values np.random.uniform returned) or, by default,
+the device draws them from the engine's counter-based generator keyed (seed, environment, episode, draw) -- the
+distribution of the reference, reproducible, and restated in tests/point_reach_oracle.py.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib_point
+from .engine import _ptr, _raw_stream
+from .spaces import Box, MDPInfo
+
+
+class BatchedPointReachEnv:
+    def __init__(self, batch, n_objects=4, random_walk=True, time_step=0.01, horizon=1000, gamma=0.99, seed=0,
+                 auto_reset=True, device='cuda:0', dtype=torch.float32):
+        """The state is zero until the first reset(): like the reference's constructor, this one does not reset (the
+        circle centres of random_walk=False are those of the FIRST reset, for the life of the object)."""
+        lib = _lib_point.load()
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ValueError("the engine runs on a ROCm device ('cuda:N'); there is no CPU path")
+        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError('dtype must be torch.float32 or torch.float64')
+        self.dtype = dtype
+        cfg = _lib_point.default_config()
+        cfg.batch, cfg.n_objects, cfg.random_walk = int(batch), int(n_objects), int(bool(random_walk))
+        cfg.dtype = _lib_point.F32 if dtype == torch.float32 else _lib_point.F64
+        cfg.horizon, cfg.auto_reset, cfg.seed = int(horizon), int(bool(auto_reset)), int(seed) & 0x7fffffff
+        cfg.dt, cfg.gamma = float(time_step), float(gamma)
+        self.cfg, self.batch, self.n_objects, self.random_walk = cfg, int(batch), int(n_objects), bool(random_walk)
+        n = self.n_objects
+        self.obs_dim, self.state_dim = 4 * (1 + n), 7 * n + 8
+        self.dims = {'q': 2, 'f': 0, 'g': n, 'null': 2, 'c': n}
+        self._h = None
+        h = C.c_void_p()
+        _lib_point.check(lib.atacom_point_create(C.byref(cfg), self._dev_index, C.byref(h)))
+        self._h, self._lib = h, lib
+        # collision_avoidance_base.py:12-14
+        self._mdp_info = MDPInfo(Box(-np.ones(self.obs_dim) * 10, np.ones(self.obs_dim) * 10), Box(-np.ones(2), np.ones(2)),
+                                 cfg.gamma, cfg.horizon)
+
+    # ------------------------------------------------------------------ reference surface
+    @property
+    def info(self):
+        return self._mdp_info
+
+    def seed(self, seed):
+        """Re-keys the device generator from the next call on."""
+        self.cfg.seed = int(seed) & 0x7fffffff
+        _lib_point.check(self._lib.atacom_point_set_seed(self._h, self.cfg.seed))
+
+    def render(self):
+        pass
+
+    def stop(self):
+        pass
+
+    def _stream(self):
+        if _raw_stream is not None:
+            return _raw_stream(self._dev_index)
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _as_dev(self, x, shape, dtype=None):
+        t = torch.as_tensor(x, dtype=dtype or self.dtype, device=self.device)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
+        return t.contiguous()
+
+    def _empty(self, *shape, dtype=None):
+        return torch.empty(shape, device=self.device, dtype=dtype or self.dtype)
+
+    def reset(self, mask=None, draws=None):
+        """Reset the masked environments (all if mask is None).  draws (optional) [B, n_objects, 2]: the obstacle
+        positions, values of U(2, 8).  Returns the observation of every environment."""
+        m = None if mask is None else self._as_dev(mask, (self.batch,), torch.uint8)
+        d = None if draws is None else self._as_dev(draws, (self.batch, self.n_objects, 2))
+        obs = self._empty(self.batch, self.obs_dim)
+        _lib_point.check(self._lib.atacom_point_reset(self._h, _ptr(m), _ptr(d), _ptr(obs), self._stream()))
+        return obs
+
+    def step(self, actions, draws=None):
+        """actions [B, 2]; draws (optional) [B, n_objects, 2], values of U(-1, 1) for the random walk.
+        -> (obs, reward, absorbing, {'last': ...}) in fresh tensors."""
+        B = self.batch
+        a = self._as_dev(actions, (B, 2))
+        d = None if draws is None else self._as_dev(draws, (B, self.n_objects, 2))
+        obs, reward = self._empty(B, self.obs_dim), self._empty(B)
+        absorbing, last = self._empty(B, dtype=torch.uint8), self._empty(B, dtype=torch.uint8)
+        _lib_point.check(self._lib.atacom_point_step(self._h, _ptr(a), _ptr(d), _ptr(obs), _ptr(reward), _ptr(absorbing),
+                                                     _ptr(last), self._stream()))
+        return obs, reward, absorbing.view(torch.bool), {'last': last.view(torch.bool)}
+
+    def _check_io(self, t, shape, dtype, what):
+        if t is None:
+            return
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or \
+                (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self._dev_index:
+            raise ValueError("%s must be a torch tensor on %s" % (what, self.device))
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s (got %s, %s)"
+                             % (what, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+
+    def step_into(self, actions, obs, reward, absorbing, last=None, draws=None):
+        """Allocation-free variant of step(): caller-owned output tensors (uint8 for the flags)."""
+        B = self.batch
+        self._check_io(actions, (B, 2), self.dtype, 'actions')
+        self._check_io(draws, (B, self.n_objects, 2), self.dtype, 'draws')
+        self._check_io(obs, (B, self.obs_dim), self.dtype, 'obs')
+        self._check_io(reward, (B,), self.dtype, 'reward')
+        self._check_io(absorbing, (B,), torch.uint8, 'absorbing')
+        self._check_io(last, (B,), torch.uint8, 'last')
+        _lib_point.check(self._lib.atacom_point_step(self._h, _ptr(actions), _ptr(draws), _ptr(obs), _ptr(reward),
+                                                     _ptr(absorbing), _ptr(last), self._stream()))
+
+    def rollout(self, actions, draws=None, want_next_obs=True, out=None):
+        """T env steps in one kernel launch.  actions [T, B, 2], draws (optional) [T, B, n_objects, 2]
+        -> dict(obs, next_obs, reward, absorbing, last, action), the layout of BatchedAtacomEnv.rollout."""
+        T = int(actions.shape[0])
+        B, D = self.batch, self.obs_dim
+        a = self._as_dev(actions, (T, B, 2))
+        d = None if draws is None else self._as_dev(draws, (T, B, self.n_objects, 2))
+        if out is None:
+            out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D) if want_next_obs else None,
+                   'reward': self._empty(T, B), 'absorbing': self._empty(T, B, dtype=torch.uint8),
+                   'last': self._empty(T, B, dtype=torch.uint8)}
+        _lib_point.check(self._lib.atacom_point_rollout(self._h, T, _ptr(a), _ptr(d), _ptr(out['obs']),
+                                                        _ptr(out.get('next_obs')), _ptr(out['reward']),
+                                                        _ptr(out['absorbing']), _ptr(out['last']), self._stream()))
+        out['action'] = a
+        return out
+
+    def rollout_policy(self, policy, n_steps):
+        """A HOST LOOP of policy.forward + step, n_steps launches of each: this task has no fused policy kernel (the
+        in-kernel MLP of BatchedAtacomEnv.rollout_policy belongs to the other library).  `policy` is any callable /
+        module mapping observations [B, obs_dim] to actions [B, 2].  Starts from the current observation; returns the
+        dict of rollout()."""
+        T, B, D = int(n_steps), self.batch, self.obs_dim
+        out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D), 'action': self._empty(T, B, 2),
+               'reward': self._empty(T, B), 'absorbing': self._empty(T, B, dtype=torch.uint8),
+               'last': self._empty(T, B, dtype=torch.uint8)}
+        fwd = policy.forward if hasattr(policy, 'forward') else policy
+        obs = self.get_state()[:, :D].contiguous()
+        with torch.no_grad():
+            for t in range(T):
+                out['obs'][t] = obs
+                out['action'][t] = fwd(obs).to(self.dtype)
+                self.step_into(out['action'][t], out['next_obs'][t], out['reward'][t], out['absorbing'][t], out['last'][t])
+                # after an in-kernel reset the next observation is the reset state, not the terminal one
+                obs = self.get_state()[:, :D].contiguous() if self.cfg.auto_reset else out['next_obs'][t]
+        return out
+
+    def get_constraints_logs(self, clear=True):
+        """(c_avg, c_max, c_dq_max) over every step of every environment since the last clear; c_dq_max is the
+        reference's constant 0 (collision_avoidance_atacom.py:40-41)."""
+        res = (C.c_double * 3)()
+        _lib_point.check(self._lib.atacom_point_get_stats(self._h, C.byref(res), int(clear), self._stream()))
+        return float(res[0]), float(res[1]), float(res[2])
+
+    def get_state(self):
+        """[B, 7 n + 8] = [observation, s, first-reset centres, _time, steps taken, episodes started, centres set]."""
+        st = self._empty(self.batch, self.state_dim)
+        _lib_point.check(self._lib.atacom_point_get_state(self._h, _ptr(st), self._stream()))
+        return st
+
+    def set_state(self, state):
+        st = self._as_dev(state, (self.batch, self.state_dim))
+        _lib_point.check(self._lib.atacom_point_set_state(self._h, _ptr(st), self._stream()))
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.atacom_point_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class PointReachAtacom:
+    """collision_avoidance_atacom.py:8-17, argument for argument; numpy in, numpy copies out.  The obstacles' draws come
+    from the device generator (seed()); `reset(draws=...)` / `step(a, draws=...)` replay recorded ones."""
+
+    def __init__(self, time_step=0.01, horizon=1000, gamma=0.99, n_objects=4, random_walk=False, device='cuda:0',
+                 dtype=torch.float32):
+        self.time_step, self.n_objects, self.random_walk = time_step, n_objects, random_walk
+        # mushroom_rl.Core resets between episodes, so the facade does not reset inside a step
+        self._engine = BatchedPointReachEnv(1, n_objects=n_objects, random_walk=random_walk, time_step=time_step,
+                                            horizon=horizon, gamma=gamma, auto_reset=False, device=device, dtype=dtype)
+        self.dims = self._engine.dims
+        self.state = np.zeros(self._engine.obs_dim)
+
+    @property
+    def info(self):
+        return self._engine.info
+
+    @property
+    def s(self):
+        n = self.n_objects
+        return self._engine.get_state()[0, 4 * (1 + n):4 * (1 + n) + n].cpu().numpy().astype(np.float64)
+
+    def seed(self, seed):
+        self._engine.seed(seed)
+
+    def render(self):
+        pass
+
+    def stop(self):
+        self._engine.stop()
+
+    def reset(self, state=None, draws=None):
+        """`state` is accepted and ignored, as in the reference (collision_avoidance_base.py:25-39)."""
+        d = None if draws is None else np.asarray(draws, dtype=np.float64).reshape(1, self.n_objects, 2)
+        self.state = self._engine.reset(draws=d)[0].cpu().numpy().astype(np.float64)
+        return self.state.copy()
+
+    def step(self, action, draws=None):
+        a = np.asarray(action, dtype=np.float64).reshape(1, 2)
+        d = None if draws is None else np.asarray(draws, dtype=np.float64).reshape(1, self.n_objects, 2)
+        obs, r, ab, _ = self._engine.step(a, draws=d)
+        host = torch.cat([obs[0], r, ab.to(obs.dtype)]).cpu().numpy().astype(np.float64)
+        self.state = host[:-2].copy()
+        return self.state.copy(), float(host[-2]), bool(host[-1] != 0.0), {}
+
+    def get_constraints_logs(self):
+        return self._engine.get_constraints_logs()
