@@ -1,4 +1,4 @@
-"""Build libatacom_hip.so and libatacom_point.so in-tree with hipcc for gfx950 (no GPU needed: hipcc cross-compiles).
+"""Build libatacom_hip.so, libatacom_point.so and libatacom_point_policy.so in-tree with hipcc for gfx950 (no GPU needed: hipcc cross-compiles).
 
     python -m rl_on_manifold_amd.build [--force]
 
@@ -33,18 +33,38 @@ UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterat
 # its kernels stay out of the main library's census and it shares only headers (the solver of atacom_linalg.h) with it.
 LIB_POINT = os.environ.get('ATACOM_POINT_LIB_OUT') or os.path.join(HERE, 'libatacom_point.so')
 UNITS_POINT = ['atacom_point.hip', 'atacom_point_capi.cpp']
-_POINT_ONLY = ('atacom_point.hip', 'atacom_point_capi.cpp', 'atacom_point.h', 'atacom_point_ops.h')
+_POINT_ONLY = ('atacom_point.hip', 'atacom_point_capi.cpp', 'atacom_point.h', 'atacom_point_ops.h', 'atacom_point_handle.h')
+
+# The task's rollout with the actor network evaluated in the kernel is a third library, libatacom_point_policy.so
+# (include/atacom_point_policy_hip.h): it borrows the handles of libatacom_point.so (csrc/atacom_point_handle.h) and keeps
+# the kernel census of the other two as it is.
+LIB_POINT_POLICY = os.environ.get('ATACOM_POINT_POLICY_LIB_OUT') or os.path.join(HERE, 'libatacom_point_policy.so')
+UNITS_POINT_POLICY = ['atacom_point_policy.hip', 'atacom_point_policy_capi.cpp']
+_POINT_POLICY_ONLY = ('atacom_point_policy.hip', 'atacom_point_policy_capi.cpp', 'atacom_point_policy.h',
+                      'atacom_point_policy_ops.h')
+
+
+def _include(name):
+    return os.path.join(os.path.dirname(HERE), 'include', name)
 
 
 def _sources():
-    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in _POINT_ONLY]
-    out.append(os.path.join(os.path.dirname(HERE), 'include', 'atacom_hip.h'))
+    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in _POINT_ONLY + _POINT_POLICY_ONLY]
+    out.append(_include('atacom_hip.h'))
     return out
 
 
 def _sources_point():
-    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h') or f in _POINT_ONLY]
-    out.append(os.path.join(os.path.dirname(HERE), 'include', 'atacom_point_hip.h'))
+    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
+           if (f.endswith('.h') or f in _POINT_ONLY) and f not in _POINT_POLICY_ONLY]
+    out.append(_include('atacom_point_hip.h'))
+    return out
+
+
+def _sources_point_policy():
+    """Every header of csrc/ (the kernel includes atacom_point.h and atacom_policy.h), the handle's, and its own units."""
+    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h') or f in _POINT_POLICY_ONLY]
+    out += [_include('atacom_hip.h'), _include('atacom_point_hip.h'), _include('atacom_point_policy_hip.h')]
     return out
 
 
@@ -61,6 +81,10 @@ def needs_build():
 
 def needs_build_point():
     return _stale(LIB_POINT, _sources_point())
+
+
+def needs_build_point_policy():
+    return _stale(LIB_POINT_POLICY, _sources_point_policy())
 
 
 # kernel-tuning builds: ATACOM_KEEP_OBJ=1 keeps the objects of a build; ATACOM_ONLY_UNITS=a.hip,b.hip then recompiles only
@@ -121,26 +145,39 @@ def build(force=False, verbose=True):
     return LIB
 
 
-def build_point(force=False, verbose=True):
-    """libatacom_point.so: the second target (two units, a few seconds)."""
-    if not force and not needs_build_point():
-        return LIB_POINT
+def _build_small(lib, units, verbose):
     if verbose:
-        print('[atacom] building %s for %s ...' % (os.path.basename(LIB_POINT), ARCH), flush=True)
-    with ThreadPoolExecutor(max_workers=len(UNITS_POINT)) as ex:
-        objs = list(ex.map(_compile, UNITS_POINT))
-    cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB_POINT] + objs
+        print('[atacom] building %s for %s ...' % (os.path.basename(lib), ARCH), flush=True)
+    with ThreadPoolExecutor(max_workers=len(units)) as ex:
+        objs = list(ex.map(_compile, units))
+    cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', lib] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('link failed:\n%s\n%s' % (' '.join(cmd), r.stderr[-4000:]))
     if not os.environ.get('ATACOM_KEEP_OBJ'):
         for o in objs:
             os.remove(o)
-    return LIB_POINT
+    return lib
+
+
+def build_point(force=False, verbose=True):
+    """libatacom_point.so: the second target (two units, a few seconds)."""
+    if not force and not needs_build_point():
+        return LIB_POINT
+    return _build_small(LIB_POINT, UNITS_POINT, verbose)
+
+
+def build_point_policy(force=False, verbose=True):
+    """libatacom_point_policy.so: the third target (two units; the four policy kernels take about a minute)."""
+    if not force and not needs_build_point_policy():
+        return LIB_POINT_POLICY
+    return _build_small(LIB_POINT_POLICY, UNITS_POINT_POLICY, verbose)
 
 
 if __name__ == '__main__':
     build(force='--force' in sys.argv)
     build_point(force='--force' in sys.argv)
+    build_point_policy(force='--force' in sys.argv)
     print(LIB)
     print(LIB_POINT)
+    print(LIB_POINT_POLICY)

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <string>
 
+#include "atacom_point_handle.h"
 #include "atacom_point_ops.h"
 
 namespace {
@@ -48,15 +49,7 @@ constexpr int kStatBlocks = 256;
 
 }  // namespace
 
-struct atacom_point_handle {
-    atacom_point_config cfg;
-    const atacom_point::PointOps* ops;
-    int device;
-    void* f;
-    int* ip;
-    double* partial_dev;
-    double* partial_host;
-};
+// struct atacom_point_handle: atacom_point_handle.h (libatacom_point_policy.so borrows the handles created here)
 
 namespace {
 // observation rows are written four elements at a time
@@ -100,6 +93,7 @@ int atacom_point_create(const atacom_point_config* cfg, int device, atacom_point
         return fail(ATACOM_POINT_E_UNSUPPORTED, "atacom_point_create: n_objects = " + std::to_string(cfg->n_objects) +
                                                     " is not compiled in (kernels exist for 2 and 4 obstacles)");
     atacom_point_handle* h = new atacom_point_handle();
+    h->magic = atacom_point::kHandleMagic;
     h->cfg = *cfg;
     h->ops = ops;
     h->device = device;
@@ -134,6 +128,7 @@ int atacom_point_destroy(atacom_point_handle* h) {
     if (h->ip) (void)hipFree(h->ip);
     if (h->partial_dev) (void)hipFree(h->partial_dev);
     if (h->partial_host) (void)hipHostFree(h->partial_host);
+    h->magic = 0;
     delete h;
     return ATACOM_POINT_OK;
 }

@@ -4,7 +4,8 @@ atacom/environments/collision_avoidance/collision_avoidance_atacom.py:8) on liba
   BatchedPointReachEnv   B environments on one device, torch tensors in and out, the surface of BatchedAtacomEnv
   PointReachAtacom       batch-1 numpy facade with the reference's constructor, argument for argument
 
-All arithmetic happens in the library (hand-written HIP, gfx950); this file only moves pointers.
+All arithmetic happens in the libraries (hand-written HIP, gfx950); this file only moves pointers.  Collection with an
+MlpPolicy (rollout_policy, rollout_packed) runs the fused kernel of libatacom_point_policy.so on the same handle.
 
 Random numbers.  The reference draws the obstacles' reset positions and random-walk accelerations from numpy's global
 generator.  Here a call either receives the draws (`draws=`, the values np.random.uniform returned) or, by default,
@@ -16,7 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib_point
+from . import _lib_point, _lib_point_policy
 from .engine import _ptr, _raw_stream
 from .spaces import Box, MDPInfo
 
@@ -141,11 +142,44 @@ class BatchedPointReachEnv:
         out['action'] = a
         return out
 
-    def rollout_policy(self, policy, n_steps):
-        """A HOST LOOP of policy.forward + step, n_steps launches of each: this task has no fused policy kernel (the
-        in-kernel MLP of BatchedAtacomEnv.rollout_policy belongs to the other library).  `policy` is any callable /
-        module mapping observations [B, obs_dim] to actions [B, 2].  Starts from the current observation; returns the
-        dict of rollout()."""
+    def _on_my_device(self, t):
+        return t.device.type == 'cuda' and t.device.index == self._dev_index
+
+    @property
+    def record_dim(self):
+        """Values of one packed record: [obs | action(2) | reward | next_obs | absorbing | last]."""
+        return 2 * self.obs_dim + 5
+
+    def _policy_lib(self):
+        if getattr(self, '_plib', None) is None:
+            self._plib = _lib_point_policy.load()
+        return self._plib
+
+    def rollout_policy(self, policy, n_steps, noise=None, draws=None, want_next_obs=True):
+        """T = n_steps env steps driven by a policy; returns the dict of rollout(), 'action' being what the policy drew.
+
+        * `policy` is an MlpPolicy (anything with `as_struct`): the FUSED kernel of libatacom_point_policy.so -- actor network
+          and exploration evaluated inside the rollout kernel, ONE launch for the whole phase.  `noise` [T, B, 2] standard-normal
+          draws supplied by the caller (None = zeros), `draws` [T, B, n_objects, 2] values of U(-1, 1) for the random walk
+          (None = the device generator, the keys of rollout()).
+        * `policy` is any other callable / module mapping observations [B, obs_dim] to actions [B, 2]: a HOST LOOP of
+          policy.forward + step, n_steps launches of each, starting from the current observation (`noise` and `draws` are not
+          taken there: the callable owns its exploration)."""
+        if hasattr(policy, 'as_struct'):
+            T, B, D, n = int(n_steps), self.batch, self.obs_dim, self.n_objects
+            net = policy.as_struct(self)
+            nz = None if noise is None else self._as_dev(noise, (T, B, 2))
+            d = None if draws is None else self._as_dev(draws, (T, B, n, 2))
+            out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D) if want_next_obs else None,
+                   'action': self._empty(T, B, 2), 'reward': self._empty(T, B),
+                   'absorbing': self._empty(T, B, dtype=torch.uint8), 'last': self._empty(T, B, dtype=torch.uint8)}
+            _lib_point_policy.check(self._policy_lib().atacom_point_policy_rollout(
+                self._h, T, C.byref(net), _ptr(nz), _ptr(d), _ptr(out['obs']), _ptr(out['next_obs']), _ptr(out['action']),
+                _ptr(out['reward']), _ptr(out['absorbing']), _ptr(out['last']), self._stream()))
+            return out
+        if noise is not None or draws is not None:
+            raise ValueError("noise / draws go with an MlpPolicy (the fused kernel); a plain callable runs the host loop and "
+                             "owns its exploration")
         T, B, D = int(n_steps), self.batch, self.obs_dim
         out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D), 'action': self._empty(T, B, 2),
                'reward': self._empty(T, B), 'absorbing': self._empty(T, B, dtype=torch.uint8),
@@ -160,6 +194,48 @@ class BatchedPointReachEnv:
                 # after an in-kernel reset the next observation is the reset state, not the terminal one
                 obs = self.get_state()[:, :D].contiguous() if self.cfg.auto_reset else out['next_obs'][t]
         return out
+
+    def rollout_packed(self, actions=None, policy=None, n_steps=None, noise=None, draws=None, out=None, batch_stride=None):
+        """T env steps in one launch, written as ONE packed record per (step, env): records [T, batch_stride, record_dim] =
+        [obs | action | reward | next_obs | absorbing | last] -- the layout the sharded collector all-gathers as it is
+        (rollout.py), the surface of BatchedAtacomEnv.rollout_packed.  Either `actions` [T, B, 2] or `policy` (an MlpPolicy,
+        evaluated inside the kernel; `noise` [T, B, 2] or None) with `n_steps`; `draws` as in rollout_policy.  batch_stride >
+        batch pads the env axis (ragged shards); the padding rows are zero (filled at allocation, or here when the caller
+        supplies `out`) and never written by the kernel."""
+        B, n, F = self.batch, self.n_objects, self.record_dim
+        if (actions is None) == (policy is None):
+            raise ValueError("give either actions or policy")
+        T = int(actions.shape[0]) if actions is not None else int(n_steps)
+        ld = B if batch_stride is None else int(batch_stride)
+        if out is None:
+            alloc = torch.empty if ld == B else torch.zeros
+            out = alloc((T, ld, F), device=self.device, dtype=self.dtype)
+        elif tuple(out.shape) != (T, ld, F) or not out.is_contiguous() or out.dtype != self.dtype \
+                or not self._on_my_device(out):
+            raise ValueError("out must be a contiguous [%d, %d, %d] tensor of the engine's dtype on %s" % (T, ld, F, self.device))
+        elif ld > B:
+            out[:, B:].zero_()                  # a caller's buffer may hold anything: the padding rows are zero (rollout.py)
+        d = None if draws is None else self._as_dev(draws, (T, B, n, 2))
+        lib = self._policy_lib()
+        if actions is not None:
+            a = self._as_dev(actions, (T, B, 2))
+            _lib_point_policy.check(lib.atacom_point_policy_rollout_packed(self._h, T, _ptr(a), None, None, _ptr(d), _ptr(out),
+                                                                           ld, self._stream()))
+        else:
+            if not hasattr(policy, 'as_struct'):
+                raise ValueError("rollout_packed takes an MlpPolicy (as_struct); a plain callable goes through rollout_policy")
+            net = policy.as_struct(self)
+            nz = None if noise is None else self._as_dev(noise, (T, B, 2))
+            _lib_point_policy.check(lib.atacom_point_policy_rollout_packed(self._h, T, None, C.byref(net), _ptr(nz), _ptr(d),
+                                                                           _ptr(out), ld, self._stream()))
+        return out
+
+    def unpack_records(self, rec):
+        """Views into packed records [..., record_dim] (no copy)."""
+        D, k = self.obs_dim, 2
+        return {'obs': rec[..., :D], 'action': rec[..., D:D + k], 'reward': rec[..., D + k],
+                'next_obs': rec[..., D + k + 1:2 * D + k + 1], 'absorbing': rec[..., 2 * D + k + 1] > 0.5,
+                'last': rec[..., 2 * D + k + 2] > 0.5}
 
     def get_constraints_logs(self, clear=True):
         """(c_avg, c_max, c_dq_max) over every step of every environment since the last clear; c_dq_max is the
