@@ -6,6 +6,9 @@ CPU / PyTorch fallback anywhere in the package.
 import ctypes as C
 import os
 
+from . import _binding
+from ._binding import AtacomError  # noqa: F401
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # ATACOM_LIB lets kernel-tuning experiments point at an alternative build of the same library
 LIB_PATH = os.environ.get('ATACOM_LIB') or os.path.join(HERE, 'libatacom_hip.so')
@@ -14,12 +17,6 @@ ENV_CIRCLE, ENV_PLANAR, ENV_IIWA, ENV_CIRCLE_EC, ENV_CIRCLE_T = 0, 1, 2, 3, 4
 F32, F64 = 0, 1
 OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
 MAX_C, MAX_Q = 12, 6
-
-EXPORTS = ['atacom_snapshot_bytes', 'atacom_snapshot_save', 'atacom_snapshot_restore', 'atacom_rollout_mlp', 'atacom_rollout_packed', 'atacom_rollout_compact', 'atacom_get_aux_state', 'atacom_set_aux_state',
-           'atacom_inverse_dynamics', 'atacom_forward_dynamics', 'atacom_default_config', 'atacom_get_dims', 'atacom_create', 'atacom_destroy', 'atacom_reset',
-           'atacom_step', 'atacom_rollout', 'atacom_get_stats', 'atacom_get_state', 'atacom_set_state',
-           'atacom_nullspace', 'atacom_constraint_terms', 'atacom_step_masked', 'atacom_canonical_mu', 'atacom_last_error', 'atacom_version', 'atacom_get_lanes',
-           'atacom_get_filter_state', 'atacom_set_filter_state', 'atacom_set_seed', 'atacom_get_policy_lanes']
 
 
 class AtacomConfig(C.Structure):
@@ -63,72 +60,51 @@ class AtacomDims(C.Structure):
                 ('record_dim', C.c_int32)]
 
 
-class AtacomError(RuntimeError):
-    pass
-
-
-_lib = None
+_vp, _i32, _u8p, _int = C.c_void_p, C.c_int32, C.c_void_p, C.c_int
+_cfg, _mlp = C.POINTER(AtacomConfig), C.POINTER(AtacomMlp)
+# {symbol: (restype, argtypes)}: every function of include/atacom_hip.h
+SIGNATURES = {
+    'atacom_last_error': (C.c_char_p, None),
+    'atacom_version': (C.c_char_p, None),
+    'atacom_default_config': (_int, [_i32, _cfg]),
+    'atacom_get_dims': (_int, [_i32, C.POINTER(AtacomDims)]),
+    'atacom_create': (_int, [_cfg, C.c_int, C.POINTER(_vp)]),
+    'atacom_destroy': (_int, [_vp]),
+    'atacom_reset': (_int, [_vp, _u8p, _vp, _vp, _vp]),
+    'atacom_step': (_int, [_vp, _vp, _vp, _vp, _u8p, _u8p, _vp]),
+    'atacom_step_masked': (_int, [_vp, _u8p, _vp, _vp, _vp, _u8p, _u8p, _vp]),
+    'atacom_canonical_mu': (_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    'atacom_rollout': (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _u8p, _u8p, _vp]),
+    'atacom_rollout_mlp': (_int, [_vp, _i32, _mlp, _vp, _vp, _vp, _vp, _vp, _u8p, _u8p, _vp]),
+    'atacom_rollout_packed': (_int, [_vp, _i32, _vp, _mlp, _vp, _vp, _i32, _vp]),
+    'atacom_rollout_compact': (_int, [_vp, _i32, _vp, _mlp, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+    'atacom_get_stats': (_int, [_vp, C.POINTER(C.c_double * 3), _i32, _vp]),
+    'atacom_get_lanes': (_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    'atacom_get_policy_lanes': (_int, [_vp, C.POINTER(_i32)]),
+    'atacom_set_seed': (_int, [_vp, _i32]),
+    'atacom_get_state': (_int, [_vp, _vp, _vp]),
+    'atacom_set_state': (_int, [_vp, _vp, _vp]),
+    'atacom_get_aux_state': (_int, [_vp, _vp, _vp]),
+    'atacom_set_aux_state': (_int, [_vp, _vp, _vp]),
+    'atacom_get_filter_state': (_int, [_vp, _vp, _vp]),
+    'atacom_set_filter_state': (_int, [_vp, _vp, _vp]),
+    'atacom_snapshot_bytes': (C.c_int64, [_vp]),
+    'atacom_snapshot_save': (_int, [_vp, _vp, _vp]),
+    'atacom_snapshot_restore': (_int, [_vp, _vp, _vp]),
+    'atacom_inverse_dynamics': (_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'atacom_forward_dynamics': (_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'atacom_nullspace': (_int, [_i32, _i32, _i32, _i32, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    'atacom_constraint_terms': (_int, [_cfg, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def load():
     """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # The process must use ONE HIP runtime.  PyTorch-ROCm bundles its own libamdhip64; if libatacom_hip.so were
-    # dlopen'ed first it would pull in /opt/rocm's copy and the two runtimes would fight over the device (observed:
-    # hipGetDeviceCount -> "no ROCm-capable device").  Importing torch first makes the .so bind to torch's runtime.
-    try:
-        import torch  # noqa: F401
-    except Exception:  # noqa: BLE001  (a pure-C consumer of the ABI does not need torch)
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise AtacomError("libatacom_hip.so is not built (%s). Run `python -m rl_on_manifold_amd.build` -- "
-                          "there is no CPU fallback." % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    vp, i32, u8p = C.c_void_p, C.c_int32, C.c_void_p
-    lib.atacom_default_config.argtypes = [i32, C.POINTER(AtacomConfig)]
-    lib.atacom_get_dims.argtypes = [i32, C.POINTER(AtacomDims)]
-    lib.atacom_create.argtypes = [C.POINTER(AtacomConfig), C.c_int, C.POINTER(vp)]
-    lib.atacom_destroy.argtypes = [vp]
-    lib.atacom_reset.argtypes = [vp, u8p, vp, vp, vp]
-    lib.atacom_step.argtypes = [vp, vp, vp, vp, u8p, u8p, vp]
-    lib.atacom_step_masked.argtypes = [vp, u8p, vp, vp, vp, u8p, u8p, vp]
-    lib.atacom_canonical_mu.argtypes = [i32, i32, i32, vp, vp, vp, vp, C.c_double, vp, vp]
-    lib.atacom_rollout.argtypes = [vp, i32, vp, vp, vp, vp, u8p, u8p, vp]
-    lib.atacom_rollout_mlp.argtypes = [vp, i32, C.POINTER(AtacomMlp), vp, vp, vp, vp, vp, u8p, u8p, vp]
-    lib.atacom_rollout_packed.argtypes = [vp, i32, vp, C.POINTER(AtacomMlp), vp, vp, i32, vp]
-    lib.atacom_rollout_compact.argtypes = [vp, i32, vp, C.POINTER(AtacomMlp), vp, vp, i32, vp, i32, vp, vp]
-    lib.atacom_get_stats.argtypes = [vp, C.POINTER(C.c_double * 3), i32, vp]
-    lib.atacom_get_lanes.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-    lib.atacom_get_policy_lanes.argtypes = [vp, C.POINTER(i32)]
-    lib.atacom_set_seed.argtypes = [vp, i32]
-    lib.atacom_get_state.argtypes = [vp, vp, vp]
-    lib.atacom_set_state.argtypes = [vp, vp, vp]
-    lib.atacom_get_aux_state.argtypes = [vp, vp, vp]
-    lib.atacom_snapshot_bytes.argtypes = [vp]
-    lib.atacom_snapshot_save.argtypes = [vp, vp, vp]
-    lib.atacom_snapshot_restore.argtypes = [vp, vp, vp]
-    lib.atacom_set_aux_state.argtypes = [vp, vp, vp]
-    lib.atacom_get_filter_state.argtypes = [vp, vp, vp]
-    lib.atacom_set_filter_state.argtypes = [vp, vp, vp]
-    lib.atacom_inverse_dynamics.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.atacom_forward_dynamics.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp]
-    lib.atacom_nullspace.argtypes = [i32, i32, i32, i32, vp, vp, C.c_double, vp, vp, vp, vp]
-    lib.atacom_constraint_terms.argtypes = [C.POINTER(AtacomConfig), i32, vp, vp, vp, vp, vp, vp]
-    lib.atacom_last_error.restype = C.c_char_p
-    lib.atacom_version.restype = C.c_char_p
-    for name in EXPORTS:
-        if name not in ('atacom_last_error', 'atacom_version', 'atacom_snapshot_bytes'):
-            getattr(lib, name).restype = C.c_int
-    lib.atacom_snapshot_bytes.restype = C.c_int64
-    _lib = lib
-    return lib
+    return _binding.load(LIB_PATH, 'libatacom_hip.so', SIGNATURES)
 
 
-def check(rc):
-    if rc != 0:
-        raise AtacomError(load().atacom_last_error().decode())
+check = _binding.checker(load, 'atacom_last_error')
 
 
 def default_config(env_id):

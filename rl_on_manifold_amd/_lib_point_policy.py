@@ -7,43 +7,29 @@ Like _lib.py: if the library is missing or cannot be loaded this module raises -
 import ctypes as C
 import os
 
-from ._lib import AtacomError, AtacomMlp
+from . import _binding
+from ._binding import AtacomError  # noqa: F401
+from ._lib import AtacomMlp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ATACOM_POINT_POLICY_LIB') or os.path.join(HERE, 'libatacom_point_policy.so')
 
 OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
 
-EXPORTS = ['atacom_point_policy_rollout', 'atacom_point_policy_rollout_packed', 'atacom_point_policy_last_error',
-           'atacom_point_policy_version']
-
-_lib = None
+_vp, _i32, _int, _mlp = C.c_void_p, C.c_int32, C.c_int, C.POINTER(AtacomMlp)
+# {symbol: (restype, argtypes)}: every function of include/atacom_point_policy_hip.h
+SIGNATURES = {
+    'atacom_point_policy_last_error': (C.c_char_p, None),
+    'atacom_point_policy_version': (C.c_char_p, None),
+    'atacom_point_policy_rollout': (_int, [_vp, _i32, _mlp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'atacom_point_policy_rollout_packed': (_int, [_vp, _i32, _vp, _mlp, _vp, _vp, _vp, _i32, _vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def load():
     """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    try:                      # one HIP runtime per process: PyTorch's, when it is there (see _lib.load)
-        import torch  # noqa: F401
-    except Exception:  # noqa: BLE001
-        pass
-    if not os.path.exists(LIB_PATH):
-        raise AtacomError("libatacom_point_policy.so is not built (%s). Run `python -m rl_on_manifold_amd.build` -- "
-                          "there is no CPU fallback." % LIB_PATH)
-    lib = C.CDLL(LIB_PATH)
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.atacom_point_policy_rollout.argtypes = [vp, i32, C.POINTER(AtacomMlp), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.atacom_point_policy_rollout_packed.argtypes = [vp, i32, vp, C.POINTER(AtacomMlp), vp, vp, vp, i32, vp]
-    lib.atacom_point_policy_last_error.restype = C.c_char_p
-    lib.atacom_point_policy_version.restype = C.c_char_p
-    lib.atacom_point_policy_rollout.restype = C.c_int
-    lib.atacom_point_policy_rollout_packed.restype = C.c_int
-    _lib = lib
-    return lib
+    return _binding.load(LIB_PATH, 'libatacom_point_policy.so', SIGNATURES)
 
 
-def check(rc):
-    if rc != 0:
-        raise AtacomError(load().atacom_point_policy_last_error().decode())
+check = _binding.checker(load, 'atacom_point_policy_last_error')

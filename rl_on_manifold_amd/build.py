@@ -1,18 +1,20 @@
-"""Build libatacom_hip.so, libatacom_point.so and libatacom_point_policy.so in-tree with hipcc for gfx950 (no GPU needed: hipcc cross-compiles).
+"""Build the package's shared libraries in-tree with hipcc for gfx950 (no GPU needed: hipcc cross-compiles).
 
     python -m rl_on_manifold_amd.build [--force]
 
-One translation unit per environment (they compile in parallel) + the C-ABI host file, linked into
-rl_on_manifold_amd/libatacom_hip.so.  The .so is git-ignored but travels to the GPU box with gpurun.
+TARGETS below describes each library: libatacom_hip.so (the air-hockey and circle tasks), libatacom_point.so (the
+collision-avoidance task) and libatacom_point_policy.so (its rollout with the actor network in the kernel).  A library is
+one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
+rl_on_manifold_amd/.  The .so files are git-ignored.
 """
 import os
 import subprocess
 import sys
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-LIB = os.environ.get('ATACOM_LIB_OUT') or os.path.join(HERE, 'libatacom_hip.so')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function'] + \
@@ -29,62 +31,73 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp']}
 
 
-# The collision-avoidance task (PointReachAtacom) is a library of its own, libatacom_point.so (include/atacom_point_hip.h):
-# its kernels stay out of the main library's census and it shares only headers (the solver of atacom_linalg.h) with it.
-LIB_POINT = os.environ.get('ATACOM_POINT_LIB_OUT') or os.path.join(HERE, 'libatacom_point.so')
-UNITS_POINT = ['atacom_point.hip', 'atacom_point_capi.cpp']
-_POINT_ONLY = ('atacom_point.hip', 'atacom_point_capi.cpp', 'atacom_point.h', 'atacom_point_ops.h', 'atacom_point_handle.h')
-
-# The task's rollout with the actor network evaluated in the kernel is a third library, libatacom_point_policy.so
-# (include/atacom_point_policy_hip.h): it borrows the handles of libatacom_point.so (csrc/atacom_point_handle.h) and keeps
-# the kernel census of the other two as it is.
-LIB_POINT_POLICY = os.environ.get('ATACOM_POINT_POLICY_LIB_OUT') or os.path.join(HERE, 'libatacom_point_policy.so')
-UNITS_POINT_POLICY = ['atacom_point_policy.hip', 'atacom_point_policy_capi.cpp']
-_POINT_POLICY_ONLY = ('atacom_point_policy.hip', 'atacom_point_policy_capi.cpp', 'atacom_point_policy.h',
-                      'atacom_point_policy_ops.h')
-
-
 def _include(name):
     return os.path.join(os.path.dirname(HERE), 'include', name)
 
 
-def _sources():
-    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in _POINT_ONLY + _POINT_POLICY_ONLY]
-    out.append(_include('atacom_hip.h'))
-    return out
+# One description per library.  `private`: the headers of csrc/ that belong to it alone; `feeds`: the libraries whose
+# private headers it includes as well; `headers`: the public headers it depends on; `tuning`: whether it takes the
+# ATACOM_ONLY_UNITS / kept-object path below.  A new library is a new entry here.
+Target = namedtuple('Target', 'lib units private feeds headers tuning')
+
+
+def _lib_out(env, name):
+    return os.environ.get(env) or os.path.join(HERE, name)
+
+
+TARGETS = {
+    'hip': Target(_lib_out('ATACOM_LIB_OUT', 'libatacom_hip.so'), UNITS, (), (), ('atacom_hip.h',), True),
+    # The collision-avoidance task (PointReachAtacom) is a library of its own (include/atacom_point_hip.h): its kernels stay
+    # out of the main library's census and it shares only headers (the solver of atacom_linalg.h, the host scaffolding of
+    # atacom_capi_common.h) with it.
+    'point': Target(_lib_out('ATACOM_POINT_LIB_OUT', 'libatacom_point.so'), ['atacom_point.hip', 'atacom_point_capi.cpp'],
+                    ('atacom_point.h', 'atacom_point_ops.h', 'atacom_point_handle.h'), (), ('atacom_point_hip.h',), False),
+    # The task's rollout with the actor network evaluated in the kernel is a third library (include/atacom_point_policy_hip.h):
+    # it borrows the handles of libatacom_point.so (csrc/atacom_point_handle.h) and keeps the kernel census of the other
+    # two as it is.
+    'point_policy': Target(_lib_out('ATACOM_POINT_POLICY_LIB_OUT', 'libatacom_point_policy.so'),
+                           ['atacom_point_policy.hip', 'atacom_point_policy_capi.cpp'],
+                           ('atacom_point_policy.h', 'atacom_point_policy_ops.h'), ('point',),
+                           ('atacom_hip.h', 'atacom_point_hip.h', 'atacom_point_policy_hip.h'), False),
+}
+_MAIN, _POINT, _POINT_POLICY = (TARGETS[k] for k in ('hip', 'point', 'point_policy'))
+LIB, LIB_POINT, LIB_POINT_POLICY = _MAIN.lib, _POINT.lib, _POINT_POLICY.lib
+UNITS_POINT, UNITS_POINT_POLICY = _POINT.units, _POINT_POLICY.units
+
+
+def _sources(target=_MAIN):
+    """What a library is rebuilt for: its own units, every header of csrc/ that is not private to a library that does not
+    feed it, and its public headers."""
+    foreign = {h for name, t in TARGETS.items() if t is not target and name not in target.feeds for h in t.private}
+    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f in target.units or (f.endswith('.h') and f not in foreign)]
+    return out + [_include(h) for h in target.headers]
 
 
 def _sources_point():
-    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
-           if (f.endswith('.h') or f in _POINT_ONLY) and f not in _POINT_POLICY_ONLY]
-    out.append(_include('atacom_point_hip.h'))
-    return out
+    return _sources(_POINT)
 
 
 def _sources_point_policy():
-    """Every header of csrc/ (the kernel includes atacom_point.h and atacom_policy.h), the handle's, and its own units."""
-    out = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h') or f in _POINT_POLICY_ONLY]
-    out += [_include('atacom_hip.h'), _include('atacom_point_hip.h'), _include('atacom_point_policy_hip.h')]
-    return out
+    return _sources(_POINT_POLICY)
 
 
-def _stale(lib, sources):
-    if not os.path.exists(lib):
+def _stale(target):
+    if not os.path.exists(target.lib):
         return True
-    t = os.path.getmtime(lib)
-    return any(os.path.getmtime(p) > t for p in sources)
+    t = os.path.getmtime(target.lib)
+    return any(os.path.getmtime(p) > t for p in _sources(target))
 
 
 def needs_build():
-    return _stale(LIB, _sources())
+    return _stale(_MAIN)
 
 
 def needs_build_point():
-    return _stale(LIB_POINT, _sources_point())
+    return _stale(_POINT)
 
 
 def needs_build_point_policy():
-    return _stale(LIB_POINT_POLICY, _sources_point_policy())
+    return _stale(_POINT_POLICY)
 
 
 # kernel-tuning builds: ATACOM_KEEP_OBJ=1 keeps the objects of a build; ATACOM_ONLY_UNITS=a.hip,b.hip then recompiles only
@@ -92,11 +105,11 @@ def needs_build_point_policy():
 ONLY = [u for u in os.environ.get('ATACOM_ONLY_UNITS', '').split(',') if u]
 
 
-def _compile(unit):
+def _compile(target, unit):
     src = os.path.join(CSRC, unit)
     tag = os.environ.get('ATACOM_OBJ_TAG', '')
     obj = os.path.join(CSRC, os.path.splitext(unit)[0] + tag + '.o')
-    if ONLY and unit in UNITS and unit not in ONLY:
+    if ONLY and target.tuning and unit not in ONLY:
         kept = os.path.join(CSRC, os.path.splitext(unit)[0] + os.environ.get('ATACOM_BASE_TAG', '_keep') + '.o')
         if not os.path.exists(kept):
             raise RuntimeError('ATACOM_ONLY_UNITS needs the kept object %s (build once with ATACOM_KEEP_OBJ=1 ATACOM_OBJ_TAG=_keep)' % kept)
@@ -123,61 +136,46 @@ def _hipcc_version():
         return 'unavailable (%s)' % e
 
 
-def build(force=False, verbose=True):
-    if not force and not needs_build():
-        return LIB
-    ver = _hipcc_version()
-    if not ver.startswith(VALIDATED_HIPCC):
-        print('[atacom] WARNING: building with "%s"; the kernels were validated with hipcc 7.2 -- run the code-object audits '
-              '(python -m pytest tests/test_kernel_resources.py) and the GPU suite before trusting this build' % ver, flush=True)
+def _build(target, force, verbose):
+    if not force and not _stale(target):
+        return target.lib
     if verbose:
-        print('[atacom] building %s for %s ...' % (os.path.basename(LIB), ARCH), flush=True)
-    with ThreadPoolExecutor(max_workers=min(len(UNITS), os.cpu_count() or 4)) as ex:
-        objs = list(ex.map(_compile, UNITS))
-    cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + objs
+        print('[atacom] building %s for %s ...' % (os.path.basename(target.lib), ARCH), flush=True)
+    with ThreadPoolExecutor(max_workers=min(len(target.units), os.cpu_count() or 4)) as ex:
+        objs = list(ex.map(lambda u: _compile(target, u), target.units))
+    cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', target.lib] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('link failed:\n%s\n%s' % (' '.join(cmd), r.stderr[-4000:]))
     if not os.environ.get('ATACOM_KEEP_OBJ'):
         for o in objs:
-            if not (ONLY and o.endswith(os.environ.get('ATACOM_BASE_TAG', '_keep') + '.o')):
+            if not (ONLY and target.tuning and o.endswith(os.environ.get('ATACOM_BASE_TAG', '_keep') + '.o')):
                 os.remove(o)
-    return LIB
+    return target.lib
 
 
-def _build_small(lib, units, verbose):
-    if verbose:
-        print('[atacom] building %s for %s ...' % (os.path.basename(lib), ARCH), flush=True)
-    with ThreadPoolExecutor(max_workers=len(units)) as ex:
-        objs = list(ex.map(_compile, units))
-    cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', lib] + objs
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError('link failed:\n%s\n%s' % (' '.join(cmd), r.stderr[-4000:]))
-    if not os.environ.get('ATACOM_KEEP_OBJ'):
-        for o in objs:
-            os.remove(o)
-    return lib
+def build(force=False, verbose=True):
+    """libatacom_hip.so: fourteen units, a few minutes."""
+    if force or needs_build():
+        ver = _hipcc_version()
+        if not ver.startswith(VALIDATED_HIPCC):
+            print('[atacom] WARNING: building with "%s"; the kernels were validated with hipcc 7.2 -- run the code-object audits '
+                  '(python -m pytest tests/test_kernel_resources.py) and the GPU suite before trusting this build' % ver, flush=True)
+    return _build(_MAIN, force, verbose)
 
 
 def build_point(force=False, verbose=True):
-    """libatacom_point.so: the second target (two units, a few seconds)."""
-    if not force and not needs_build_point():
-        return LIB_POINT
-    return _build_small(LIB_POINT, UNITS_POINT, verbose)
+    """libatacom_point.so: two units, a few seconds."""
+    return _build(_POINT, force, verbose)
 
 
 def build_point_policy(force=False, verbose=True):
-    """libatacom_point_policy.so: the third target (two units; the four policy kernels take about a minute)."""
-    if not force and not needs_build_point_policy():
-        return LIB_POINT_POLICY
-    return _build_small(LIB_POINT_POLICY, UNITS_POINT_POLICY, verbose)
+    """libatacom_point_policy.so: two units; the four policy kernels take about a minute."""
+    return _build(_POINT_POLICY, force, verbose)
 
 
 if __name__ == '__main__':
-    build(force='--force' in sys.argv)
-    build_point(force='--force' in sys.argv)
-    build_point_policy(force='--force' in sys.argv)
-    print(LIB)
-    print(LIB_POINT)
-    print(LIB_POINT_POLICY)
+    for _b in (build, build_point, build_point_policy):
+        _b(force='--force' in sys.argv)
+    for _t in TARGETS.values():
+        print(_t.lib)

@@ -13,43 +13,12 @@
 #include <utility>
 #include <vector>
 
+#include "atacom_mlp_host.h"
 #include "atacom_ops.h"
+#define ATACOM_CAPI_E_HIP ATACOM_E_HIP
+#include "atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(ATACOM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
-// Every entry point that touches a handle runs on the handle's device and puts the caller's current device back on
-// the way out (a handle on cuda:1 must not leave the calling thread -- i.e. PyTorch -- on cuda:1).
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        err = (prev == dev) ? hipSuccess : hipSetDevice(dev);
-        if (prev == dev) prev = -1;               // nothing to restore
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define ON_DEVICE(h)                \
-    DeviceGuard guard_((h)->device); \
-    HIP_TRY(guard_.err)
 
 const atacom::EnvOps* get_ops(int env_id, int dtype) {
     if (dtype != ATACOM_F32 && dtype != ATACOM_F64) return nullptr;
@@ -312,14 +281,10 @@ static hipError_t calibrate_step_lanes(atacom_handle* h) {
     return e;
 }
 
-// Validates *in and copies it to *net: a struct of the first release's size (ATACOM_MLP_SIZE_V1) gets the appended fields
-// zeroed (mean_mode = explore = 0, what it ran before they existed); its memory past that size is never read.
+// Validates *in and copies it to *net by the ABI-size rule of atacom_mlp_host.h: mlp_abi_copy.
 static int check_mlp(const atacom_handle* h, const atacom_mlp* in, const char* who, atacom_mlp* net) {
     const std::string w(who);
-    if (in->struct_size != (int32_t)sizeof(atacom_mlp) && in->struct_size != ATACOM_MLP_SIZE_V1)
-        return fail(ATACOM_E_INVALID, w + ": atacom_mlp.struct_size mismatch (ABI)");
-    std::memset(net, 0, sizeof(atacom_mlp));
-    std::memcpy(net, in, (size_t)in->struct_size);
+    if (!atacom::mlp_abi_copy(in, net)) return fail(ATACOM_E_INVALID, w + ": atacom_mlp.struct_size mismatch (ABI)");
     if (net->n_in != h->ops->obs_dim || net->n_out != h->ops->nk)
         return fail(ATACOM_E_INVALID, w + ": network n_in / n_out must equal obs_dim / n_null");
     if (!net->W1 || !net->b1 || !net->W2 || !net->b2 || !net->W3 || !net->b3)

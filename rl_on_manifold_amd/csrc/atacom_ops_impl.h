@@ -1,6 +1,7 @@
 // Instantiates the kernels of atacom_kernels.h for one environment and fills its EnvOps tables.
 #pragma once
 #include "atacom_kernels.h"
+#include "atacom_mlp_host.h"
 #include "atacom_ops.h"
 
 namespace atacom {
@@ -137,19 +138,7 @@ struct Variant {
                            const void* noise, void* obs, void* nobs, void* acts, void* rew, uint8_t* ab, uint8_t* last,
                            void* rec, int rec_ld, const CompactArgs* cx, hipStream_t s) {
         if (E::ID == 0 || net.hidden != 64) return ATACOM_E_UNSUPPORTED;
-        MlpArgs<T> a;
-        a.W1 = (const T*)net.W1; a.b1 = (const T*)net.b1; a.W2 = (const T*)net.W2; a.b2 = (const T*)net.b2;
-        a.W3 = (const T*)net.W3; a.b3 = (const T*)net.b3; a.obs_shift = (const T*)net.obs_shift;
-        a.obs_scale = (const T*)net.obs_scale; a.std = (const T*)net.std;
-        a.sW1 = (const T*)net.sW1; a.sb1 = (const T*)net.sb1; a.sW2 = (const T*)net.sW2; a.sb2 = (const T*)net.sb2;
-        a.sW3 = (const T*)net.sW3; a.sb3 = (const T*)net.sb3;
-        a.log_std_min = (T)net.log_std_min; a.log_std_max = (T)net.log_std_max; a.squash = net.squash;
-        a.n_in = net.n_in; a.n_out = net.n_out; a.activation = net.activation;
-        a.mean_mode = net.mean_mode; a.explore = net.explore;
-        a.act_scale = (const T*)net.act_scale; a.act_low = (const T*)net.act_low; a.act_high = (const T*)net.act_high;
-        a.ou_x0 = (const T*)net.ou_x0; a.ou_state = (T*)net.ou_state;
-        // x <- x - (theta dt) x + (sqrt(dt) std) eps: the two products of constants formed once, in double
-        a.ou_theta_dt = (T)(net.ou_theta * net.ou_dt); a.ou_sqrt_dt = (T)(net.explore == 2 ? std::sqrt(net.ou_dt) : 0.0);
+        const MlpArgs<T> a = mlp_args<T>(net);
         if constexpr (E::ID != 0) {
             // float64 (the parity build): the policy kernel exists for the default variant only -- reference chart, kinematic,
             // no domain randomisation -- which is what the 1e-8 parity tests of row N2 run (tests/test_gpu_parity.py)

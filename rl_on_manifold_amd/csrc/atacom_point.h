@@ -21,6 +21,7 @@
 // (profiles/point_reach.md).  Workgroups of 256: 64 and 128 were 1-5 % slower there.
 #pragma once
 #include <stdint.h>
+#include "../../include/atacom_point_hip.h"
 #include "atacom_kernels.h"          // device_uniform (the counter-based generator), num<T>, the solver via atacom_linalg.h
 
 namespace atacom_point {
@@ -33,6 +34,16 @@ struct PParams {
     unsigned int seed;
     T dt;
 };
+
+// host: the launch parameters of every kernel that takes a handle's configuration, in either library of the task
+template <typename T>
+static PParams<T> params(const atacom_point_config& c) {
+    PParams<T> P;
+    P.batch = c.batch; P.horizon = c.horizon; P.auto_reset = c.auto_reset; P.random_walk = c.random_walk;
+    P.seed = (unsigned int)c.seed;
+    P.dt = (T)c.dt;
+    return P;
+}
 
 // ------------------------------------------------------------------ persistent state
 template <int N>

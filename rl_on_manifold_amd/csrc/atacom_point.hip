@@ -5,15 +5,6 @@
 namespace atacom_point {
 namespace {
 
-template <typename T>
-PParams<T> params(const atacom_point_config& c) {
-    PParams<T> P;
-    P.batch = c.batch; P.horizon = c.horizon; P.auto_reset = c.auto_reset; P.random_walk = c.random_walk;
-    P.seed = (unsigned int)c.seed;
-    P.dt = (T)c.dt;
-    return P;
-}
-
 template <typename T, int N>
 struct Ops {
     static dim3 grid(int B) { return dim3((B + BLOCK - 1) / BLOCK); }

@@ -9,41 +9,10 @@
 
 #include "atacom_point_handle.h"
 #include "atacom_point_ops.h"
+#define ATACOM_CAPI_E_HIP ATACOM_POINT_E_HIP
+#include "atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(ATACOM_POINT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
-
-// every entry point runs on the handle's device and puts the caller's current device back on the way out
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        err = (prev == dev) ? hipSuccess : hipSetDevice(dev);
-        if (prev == dev) prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define ON_DEVICE(h)                 \
-    DeviceGuard guard_((h)->device); \
-    HIP_TRY(guard_.err)
 
 constexpr int kStatBlocks = 256;
 

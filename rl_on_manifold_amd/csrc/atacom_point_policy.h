@@ -9,9 +9,9 @@
 //   float   one environment per lane, a wave = four GEMM blocks of 16 environments: mlp_stage_mfma once per workgroup,
 //           mlp_obs_to_operand + mlp_forward_mfma<4 (1 + N), 64, 2, 4> per step (second pass for SAC's sigma network);
 //   double  mlp_stage + the VALU form mlp_forward<..., LANES = 1>.
-// The exploration block mirrors atacom_kernels.h:1392-1453 (k_rollout_mlp), operation for operation and in its order; it is
-// restated and not lifted into a shared device function because that header is compiled into the main library, whose 445
-// code objects are pinned.
+// The exploration block mirrors that of k_rollout_mlp (atacom_kernels.h), operation for operation and in its order.  It is
+// restated and not lifted into shared forced-inline device functions because such a lift changes the generated code of every
+// k_rollout_mlp instantiation (measured on the planar unit: -66 to +120 instructions per kernel): it needs an A/B on hardware.
 //
 // LDS.  float: [mean net | sigma net | per-wave staging] = 2 x 31 008 B + 40 960 B = 102 976 B, the layout mlp_stage_mfma
 // zeroes and fills (the sigma block is reserved whether or not there is one: the staging helper addresses the per-wave area

@@ -2,54 +2,24 @@
 // libatacom_point.so (atacom_point_handle.h); validates, then dispatches to the launcher; contains no numerics.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
+#include "atacom_mlp_host.h"
 #include "atacom_point_handle.h"
 #include "atacom_point_policy_ops.h"
+#define ATACOM_CAPI_E_HIP ATACOM_POINT_E_HIP
+#include "atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(ATACOM_POINT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
-
-// the launch runs on the handle's device; the caller's current device is put back on the way out
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t err;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        err = (prev == dev) ? hipSuccess : hipSetDevice(dev);
-        if (prev == dev) prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
 std::string num(long long v) { return std::to_string(v); }
 
-// Everything about *in that can be judged without a handle.  Copies it to *net: a struct of the first release's size
-// (ATACOM_MLP_SIZE_V1) gets the appended fields zeroed; its memory past that size is never read.
+// Everything about *in that can be judged without a handle.  Copies it to *net by the ABI-size rule of
+// atacom_mlp_host.h: mlp_abi_copy.
 int check_mlp(const atacom_mlp* in, const std::string& w, atacom_mlp* net) {
-    if (in->struct_size != (int32_t)sizeof(atacom_mlp) && in->struct_size != ATACOM_MLP_SIZE_V1)
+    if (!atacom::mlp_abi_copy(in, net))
         return fail(ATACOM_POINT_E_INVALID, w + ": atacom_mlp.struct_size = " + num(in->struct_size) + " is neither sizeof(atacom_mlp) = " +
                                                 num((long long)sizeof(atacom_mlp)) + " nor ATACOM_MLP_SIZE_V1 (ABI)");
-    std::memset(net, 0, sizeof(atacom_mlp));
-    std::memcpy(net, in, (size_t)in->struct_size);
     if (net->hidden != 64)
         return fail(ATACOM_POINT_E_UNSUPPORTED, w + ": hidden = " + num(net->hidden) + " is not compiled in (64 hidden units)");
     if (net->n_out != 2)
@@ -119,8 +89,7 @@ int atacom_point_policy_rollout(atacom_point_handle* h, int32_t n_steps, const a
     const uintptr_t mask = 4 * elem_size(h) - 1;             // observation rows are written four elements at a time
     if (((uintptr_t)d_obs & mask) || ((uintptr_t)d_next_obs & mask))
         return fail(ATACOM_POINT_E_INVALID, w + ": d_obs / d_next_obs must be aligned to four elements");
-    DeviceGuard guard(h->device);
-    HIP_TRY(guard.err);
+    ON_DEVICE(h);
     if (atacom_point::point_policy_launch(h->cfg, n_steps, &m, h->f, h->ip, nullptr, d_noise, d_draws, d_obs, d_next_obs,
                                           d_actions, d_reward, d_absorbing, d_last, nullptr, 0, (hipStream_t)stream))
         return fail(ATACOM_POINT_E_UNSUPPORTED, w + ": no kernel for dtype " + num(h->cfg.dtype) + ", n_objects = " + num(h->cfg.n_objects));
@@ -148,8 +117,7 @@ int atacom_point_policy_rollout_packed(atacom_point_handle* h, int32_t n_steps, 
         return fail(ATACOM_POINT_E_INVALID, w + ": record_batch_stride = " + num(record_batch_stride) + " is smaller than the batch " + num(h->cfg.batch));
     if ((uintptr_t)d_records & (elem_size(h) - 1))
         return fail(ATACOM_POINT_E_INVALID, w + ": d_records must be aligned to one element");
-    DeviceGuard guard(h->device);
-    HIP_TRY(guard.err);
+    ON_DEVICE(h);
     if (atacom_point::point_policy_launch(h->cfg, n_steps, net ? &m : nullptr, h->f, h->ip, d_actions, d_noise, d_draws, nullptr,
                                           nullptr, nullptr, nullptr, nullptr, nullptr, d_records, record_batch_stride,
                                           (hipStream_t)stream))

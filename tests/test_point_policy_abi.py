@@ -140,6 +140,28 @@ def test_the_other_libraries_units_are_unchanged():
     assert os.path.basename(build.LIB_POINT_POLICY) == 'libatacom_point_policy.so' or os.environ.get('ATACOM_POINT_POLICY_LIB_OUT')
 
 
+def test_a_touched_header_makes_exactly_the_libraries_that_include_it_stale(monkeypatch):
+    """The staleness rule of build.py (one rule over its table of targets), on faked modification times: no source is edited."""
+    from rl_on_manifold_amd import build
+    libs = (build.LIB, build.LIB_POINT, build.LIB_POINT_POLICY)
+    touched = []
+    real_exists = os.path.exists
+    monkeypatch.setattr(build.os.path, 'exists', lambda p: p in libs or real_exists(p))
+    monkeypatch.setattr(build.os.path, 'getmtime', lambda p: 2.0 if os.path.basename(p) in touched else 1.0)
+
+    def stale():
+        return [build.needs_build(), build.needs_build_point(), build.needs_build_point_policy()]
+
+    assert stale() == [False, False, False]
+    for header, want in (('atacom_point_policy.h', [False, False, True]), ('atacom_point.h', [False, True, True]),
+                         ('atacom_point_handle.h', [False, True, True]), ('atacom_linalg.h', [True, True, True]),
+                         ('atacom_capi_common.h', [True, True, True]), ('atacom_point_policy_hip.h', [False, False, True]),
+                         ('atacom_point_hip.h', [False, True, True]), ('atacom_capi.cpp', [True, False, False])):
+        touched[:] = [header]
+        assert stale() == want, header
+        assert os.path.exists(os.path.join(build.CSRC, header)) or os.path.exists(os.path.join(ROOT, 'include', header)), header
+
+
 def test_python_surface():
     import inspect
     import rl_on_manifold_amd as pkg
