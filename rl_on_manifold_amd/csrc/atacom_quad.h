@@ -102,11 +102,32 @@ __device__ __forceinline__ T pick4(const T (&z)[LEN], int slot4, int lq) {
 }
 
 // ---- quad reductions / broadcasts of two-wide vectors (vec2, splat2, fma2: atacom_linalg.h)
-// float: the two butterfly levels of 2 / 4 / 6 independent quad sums written out as v_add_f32_dpp (DPP operand
-// folded into the add).  Left to itself the compiler pairs the halves into v_pk_add_f32, which cannot take a DPP
-// operand, so every level became 2 x v_mov_dpp + v_pk_add + an s_nop for the DPP read-after-write hazard (2
-// wait states, which the assembler does not insert inside asm: the leading s_nop covers a producer issued right
-// before, the interleaving of >= 4 sums covers the second level).  Results are bitwise those of qsum().
+// float, 8 lanes (osum_n, split_sum): every butterfly level is a DPP move plus an add, which the compiler's DPP-combine
+// pass folds into ONE v_add_f32_dpp; the DPP read-after-write hazard (2 wait states) is the compiler's, which adds only the
+// wait states that are really missing.  Two things keep that form intact:
+//   * left to itself the SLP vectoriser pairs the adds of two independent sums into v_pk_add_f32, which cannot take a DPP
+//     operand (every level then is 2 x v_mov_dpp + v_pk_add + s_nop).  The RESULT of a sum therefore goes through an empty
+//     asm (opaque), which the vectoriser cannot look through and which emits nothing -- after the LAST level only: the hazard
+//     recogniser takes an asm for the definition of its register, and a barrier between two levels puts an s_nop 1 in
+//     front of the next level's DPP read;
+//   * contraction is off on the adds: a sum handed over as a bare product would otherwise be fused into an fma, and the
+//     results must stay bitwise those of qsum() (the same adds in the same butterfly order).
+// 4 lanes (qsum_n) and lane pairs (psum_n) keep hand-written asm blocks behind a leading s_nop 1 (the assembler does not
+// look inside asm, so the hazard there is the author's): measured, the compiler's form makes the planar 4-lane T-step
+// kernel 5 % slower and a 2-lane policy kernel spill.  Measurements and history: profiles/step_slot_census.md.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+#pragma clang fp contract(off)       // a sum handed over as a bare product must not be fused into this add
+    return v + dpp_mov<CTRL>(v);
+}
+__device__ __forceinline__ void opaque(float& v) { asm("" : "+v"(v)); }
+__device__ __forceinline__ void osum1(float& v) {
+    v = dpp_add<0xB1>(v);                                   // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E>(v);                                   // quad_perm [2,3,0,1]
+    v = dpp_add<DPP_ROW_HALF_MIRROR>(v);
+    opaque(v);
+}
+// quads: two levels
 #define ATACOM_DPP_X1 " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 #define ATACOM_DPP_X2 " quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
 __device__ __forceinline__ void qsum_n(float& a, float& b) {
@@ -134,36 +155,12 @@ __device__ __forceinline__ void qsum_n(float& a, float& b, float& c, float& d, f
         : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
 }
 // half rows (8 lanes): a third level through row_half_mirror
-#define ATACOM_DPP_X4 " row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-__device__ __forceinline__ void osum_n(float& a, float& b) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X1 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X1 "s_nop 0\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X2 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X2 "s_nop 0\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X4 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X4
-        : "+v"(a), "+v"(b));
-}
+__device__ __forceinline__ void osum_n(float& a, float& b) { osum1(a); osum1(b); }
 __device__ __forceinline__ void osum_n(float& a, float& b, float& c, float& d) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X1 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X1
-        "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X1 "v_add_f32_dpp %3, %3, %3" ATACOM_DPP_X1
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X2 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X2
-        "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X2 "v_add_f32_dpp %3, %3, %3" ATACOM_DPP_X2
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X4 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X4
-        "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X4 "v_add_f32_dpp %3, %3, %3" ATACOM_DPP_X4
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+    osum1(a); osum1(b); osum1(c); osum1(d);
 }
 __device__ __forceinline__ void osum_n(float& a, float& b, float& c, float& d, float& e, float& f) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X1 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X1
-        "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X1 "v_add_f32_dpp %3, %3, %3" ATACOM_DPP_X1
-        "v_add_f32_dpp %4, %4, %4" ATACOM_DPP_X1 "v_add_f32_dpp %5, %5, %5" ATACOM_DPP_X1
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X2 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X2
-        "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X2 "v_add_f32_dpp %3, %3, %3" ATACOM_DPP_X2
-        "v_add_f32_dpp %4, %4, %4" ATACOM_DPP_X2 "v_add_f32_dpp %5, %5, %5" ATACOM_DPP_X2
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X4 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X4
-        "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X4 "v_add_f32_dpp %3, %3, %3" ATACOM_DPP_X4
-        "v_add_f32_dpp %4, %4, %4" ATACOM_DPP_X4 "v_add_f32_dpp %5, %5, %5" ATACOM_DPP_X4
-        : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+    osum1(a); osum1(b); osum1(c); osum1(d); osum1(e); osum1(f);
 }
 __device__ __forceinline__ void osum_n(double& a, double& b) { a = qsum<8>(a); b = qsum<8>(b); }
 __device__ __forceinline__ void osum_n(double& a, double& b, double& c, double& d) {
@@ -172,7 +169,7 @@ __device__ __forceinline__ void osum_n(double& a, double& b, double& c, double& 
 __device__ __forceinline__ void osum_n(double& a, double& b, double& c, double& d, double& e, double& f) {
     a = qsum<8>(a); b = qsum<8>(b); c = qsum<8>(c); d = qsum<8>(d); e = qsum<8>(e); f = qsum<8>(f);
 }
-// lane pairs: one butterfly level
+// lane pairs: one butterfly level (asm, see above)
 __device__ __forceinline__ void psum_n(float& a, float& b) {
     asm("s_nop 1\n\t"
         "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X1 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X1
@@ -234,22 +231,17 @@ __device__ __forceinline__ void qsum_pairs(vec2<T> (&w)[CNT]) {
 // Y_k is the same vector as my X_k); two quad levels finish them, and Y_k = mirror(X_k) returns the other H totals:
 // 4 H cross-lane instructions instead of the butterfly's 6 H, the same bits in all eight lanes (a vector's total is formed
 // in one half and copied).  h[0..2H-1] in, totals out (in the lane's own physical order).
-#define ATACOM_DPP_HM " row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-__device__ __forceinline__ void split_sum(float (&h)[6]) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %3, %0" ATACOM_DPP_HM "v_add_f32_dpp %1, %4, %1" ATACOM_DPP_HM "v_add_f32_dpp %2, %5, %2" ATACOM_DPP_HM
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X1 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X1 "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X1
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X2 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X2 "v_add_f32_dpp %2, %2, %2" ATACOM_DPP_X2
-        "v_mov_b32_dpp %3, %0" ATACOM_DPP_HM "v_mov_b32_dpp %4, %1" ATACOM_DPP_HM "v_mov_b32_dpp %5, %2" ATACOM_DPP_HM
-        : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]), "+v"(h[4]), "+v"(h[5]));
-}
-__device__ __forceinline__ void split_sum(float (&h)[4]) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %2, %0" ATACOM_DPP_HM "v_add_f32_dpp %1, %3, %1" ATACOM_DPP_HM "s_nop 0\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X1 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X1 "s_nop 0\n\t"
-        "v_add_f32_dpp %0, %0, %0" ATACOM_DPP_X2 "v_add_f32_dpp %1, %1, %1" ATACOM_DPP_X2 "s_nop 0\n\t"
-        "v_mov_b32_dpp %2, %0" ATACOM_DPP_HM "v_mov_b32_dpp %3, %1" ATACOM_DPP_HM
-        : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]));
+template <int H2>
+__device__ __forceinline__ void split_sum(float (&h)[H2]) {
+#pragma clang fp contract(off)       // see dpp_add
+    constexpr int H = H2 / 2;
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        h[k] = dpp_add<0x4E>(dpp_add<0xB1>(dpp_mov<DPP_ROW_HALF_MIRROR>(h[H + k]) + h[k]));
+        h[H + k] = dpp_mov<DPP_ROW_HALF_MIRROR>(h[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < H2; ++k) opaque(h[k]);
 }
 template <int H2>
 __device__ __forceinline__ void split_sum(double (&h)[H2]) {
