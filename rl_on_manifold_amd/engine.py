@@ -3,30 +3,24 @@
 batch dimension.  All arithmetic happens in libatacom_hip.so (hand-written HIP, gfx950); this file
 only moves pointers: torch ROCm tensors supply device memory and the current HIP stream.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._device_env import DeviceEnv, _ptr   # _ptr: also imported from here by tests and tools
+from .rollout import compact_record_fields, record_fields
 from .spaces import Box, MDPInfo
 
 _ENV_IDS = {'circle': _lib.ENV_CIRCLE, 'A': _lib.ENV_CIRCLE, 'planar': _lib.ENV_PLANAR, 'H': _lib.ENV_PLANAR,
             'iiwa': _lib.ENV_IIWA, '7H': _lib.ENV_IIWA, 'circle_ec': _lib.ENV_CIRCLE_EC, 'E': _lib.ENV_CIRCLE_EC,
             'circle_t': _lib.ENV_CIRCLE_T, 'T': _lib.ENV_CIRCLE_T}
+_DTYPES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 
 
-def _ptr(t):
-    # a plain int (or None) converts to void* through the argtypes of _lib.py; no c_void_p object per call
-    return t.data_ptr() if t is not None else None
-
-
-# torch.cuda.current_stream(device).cuda_stream builds two Python objects per call (~2 us -- more than the circle
-# kernel runs); the raw accessor PyTorch keeps for extension launchers returns the hipStream_t as an int directly
-_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-
-
-class BatchedAtacomEnv:
+class BatchedAtacomEnv(DeviceEnv):
     """`batch` independent ATACOM environments stepped by one HIP kernel launch per call.
 
     Same method names as the reference wrapper, batched:
@@ -38,6 +32,7 @@ class BatchedAtacomEnv:
     """
 
     _warned_rigid_body = False
+    _destroy = 'atacom_destroy'
 
     def __init__(self, env, batch, device='cuda:0', dtype=torch.float32, horizon=None, gamma=None, Kc=None,
                  time_step=None, n_intermediate_steps=None, action_penalty=None, auto_reset=False,
@@ -49,16 +44,10 @@ class BatchedAtacomEnv:
             raise _lib.AtacomError("BatchedAtacomEnv needs a ROCm GPU (torch.cuda.is_available() is False); "
                                    "there is no CPU fallback")
         self.env_id = _ENV_IDS[env] if isinstance(env, str) else int(env)
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise _lib.AtacomError("device must be a ROCm GPU ('cuda:N')")
-        # normalised once: torch.device('cuda') != torch.device('cuda:0'), and every comparison below is on self.device
-        self._dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.device = torch.device('cuda', self._dev_index)
-        self.dtype = dtype
+        self._init_device(device, dtype, _lib.check, _lib.AtacomError("device must be a ROCm GPU ('cuda:N')"))
         cfg = _lib.default_config(self.env_id)
         cfg.batch = int(batch)
-        cfg.dtype = {torch.float32: _lib.F32, torch.float64: _lib.F64}[dtype]
+        cfg.dtype = _DTYPES[dtype]
         if horizon is not None:
             cfg.horizon = int(horizon)
         if gamma is not None:
@@ -123,6 +112,7 @@ class BatchedAtacomEnv:
         self.dims = {'q': d.dim_q, 'f': d.n_f, 'g': d.n_g, 'null': d.n_null, 'c': d.n_f + d.n_g}   # atacom.py:25-40
         self.obs_dim, self.state_dim, self.init_state_dim = d.obs_dim, d.state_dim, d.init_state_dim
         self.record_dim = d.record_dim
+        assert self.record_dim == record_fields(d.obs_dim, d.n_null)[1], "the library's record is not rollout.record_fields'"
         # get_dims reports the ACTION dimension in n_null: dim_q - n_f for ATACOM (atacom.py:39,51), dim_q for the
         # 'E' / 'T' baselines (error_correction_wrapper.py:48, circle_base.py:24)
         if Kc is not None:
@@ -135,12 +125,9 @@ class BatchedAtacomEnv:
         _lib.check(lib.atacom_create(C.byref(cfg), self._dev_index, C.byref(h)))
         self._h = h
         self._lib = lib
-        self._io_ok = set()
-        B, k, D = self.batch, self.dims['null'], self.obs_dim
-        self._obs = torch.empty((B, D), device=self.device, dtype=dtype)
-        self._reward = torch.empty((B,), device=self.device, dtype=dtype)
-        self._absorbing = torch.empty((B,), device=self.device, dtype=torch.uint8)
-        self._last = torch.empty((B,), device=self.device, dtype=torch.uint8)
+        B, k = self.batch, self.dims['null']
+        self._obs, self._reward = self._empty(B, self.obs_dim), self._empty(B)      # step_into buffers for tools
+        self._absorbing, self._last = self._empty(B, dtype=torch.uint8), self._empty(B, dtype=torch.uint8)
         lo, hi = self.observation_bounds(self.env_id, cfg)
         self._mdp_info = MDPInfo(Box(lo, hi), Box(-np.ones(k), np.ones(k)), cfg.gamma, cfg.horizon)   # atacom.py:50-51
         self.reset()
@@ -177,25 +164,8 @@ class BatchedAtacomEnv:
         self._seed = int(seed) & 0x7fffffff
         _lib.check(self._lib.atacom_set_seed(self._h, self._seed))
 
-    def render(self):
-        pass
-
-    def stop(self):
-        pass
-
     def set_logger(self, logger):
         self._logger = logger
-
-    def _stream(self):
-        if _raw_stream is not None:
-            return _raw_stream(self._dev_index)
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _as_dev(self, x, shape, dtype=None):
-        t = torch.as_tensor(x, dtype=dtype or self.dtype, device=self.device)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
-        return t.contiguous()
 
     def reset(self, mask=None, state=None):
         """Reset the masked envs (all if mask is None).  `state` ([B, init_state_dim] = [q, dq(, puck6)]) replaces
@@ -206,71 +176,7 @@ class BatchedAtacomEnv:
         _lib.check(self._lib.atacom_reset(self._h, _ptr(m), _ptr(s), _ptr(obs), self._stream()))
         return obs
 
-    def step(self, actions, mask=None):
-        """mask (optional, [B] bool / uint8): environments with a zero entry sit the call out ON THE DEVICE -- state, step
-        counter and statistics untouched, obs = their current observation, reward 0, flags False."""
-        a = self._as_dev(actions, (self.batch, self.dims['null']))
-        # fresh output tensors written by the kernel itself (the reference returns copies, atacom.py:115); the flags are
-        # 0 / 1 bytes, so the bool tensors are reinterpreting views -- no copy or conversion kernel follows the step
-        B = self.batch
-        obs = torch.empty((B, self.obs_dim), device=self.device, dtype=self.dtype)
-        reward = torch.empty((B,), device=self.device, dtype=self.dtype)
-        absorbing = torch.empty((B,), device=self.device, dtype=torch.uint8)
-        last = torch.empty((B,), device=self.device, dtype=torch.uint8)
-        if mask is None:
-            _lib.check(self._lib.atacom_step(self._h, _ptr(a), _ptr(obs), _ptr(reward), _ptr(absorbing), _ptr(last),
-                                              self._stream()))
-        else:
-            m = mask.view(torch.uint8) if (isinstance(mask, torch.Tensor) and mask.dtype == torch.bool
-                                           and self._on_my_device(mask) and mask.is_contiguous()) \
-                else self._as_dev(mask, (B,), torch.uint8)
-            if tuple(m.shape) != (B,):
-                raise ValueError("expected a mask of shape (%d,), got %s" % (B, tuple(m.shape)))
-            _lib.check(self._lib.atacom_step_masked(self._h, _ptr(m), _ptr(a), _ptr(obs), _ptr(reward), _ptr(absorbing),
-                                                     _ptr(last), self._stream()))
-        return obs, reward, absorbing.view(torch.bool), {'last': last.view(torch.bool)}
-
-    def _check_io(self, t, shape, dtype, what):
-        """Raw-pointer entry points read whatever they are given: a float64, strided or host tensor would be read as
-        garbage.  Validated once per distinct tensor (keyed by storage, shape, dtype), so the steady state of a loop that
-        reuses its buffers pays one dict lookup per argument and allocates nothing."""
-        if t is None:
-            return
-        if not isinstance(t, torch.Tensor) or not self._on_my_device(t):
-            raise ValueError("%s must be a torch tensor on %s" % (what, self.device))
-        key = (what, t.data_ptr(), t.dtype, tuple(t.shape), t.stride())
-        if key in self._io_ok:
-            return
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s (got %s, %s%s)"
-                             % (what, dtype, tuple(shape), t.dtype, tuple(t.shape), '' if t.is_contiguous() else ', strided'))
-        if len(self._io_ok) > 4096:
-            self._io_ok.clear()
-        self._io_ok.add(key)
-
-    def step_into(self, actions, obs, reward, absorbing, last=None, mask=None):
-        """Allocation-free variant of step(): caller-owned output tensors (uint8 for the flags).  `mask` (uint8 [B],
-        optional): environments with a zero byte sit the call out on the device (atacom_step_masked)."""
-        B = self.batch
-        self._check_io(actions, (B, self.dims['null']), self.dtype, 'actions')
-        self._check_io(obs, (B, self.obs_dim), self.dtype, 'obs')
-        self._check_io(reward, (B,), self.dtype, 'reward')
-        self._check_io(absorbing, (B,), torch.uint8, 'absorbing')
-        self._check_io(last, (B,), torch.uint8, 'last')
-        if mask is None:
-            _lib.check(self._lib.atacom_step(self._h, _ptr(actions), _ptr(obs), _ptr(reward), _ptr(absorbing),
-                                              _ptr(last), self._stream()))
-        else:
-            self._check_io(mask, (B,), torch.uint8, 'mask')
-            _lib.check(self._lib.atacom_step_masked(self._h, _ptr(mask), _ptr(actions), _ptr(obs), _ptr(reward),
-                                                     _ptr(absorbing), _ptr(last), self._stream()))
-
-    def bind_step(self, actions, obs, reward, absorbing, last=None, mask=None):
-        """step_into() with its arguments validated ONCE: returns a zero-argument callable that launches atacom_step (or
-        atacom_step_masked) on the caller's current stream with these tensors -- for loops that reuse their buffers and are
-        bound by the host (CircularMotion: the kernel runs 4 us, five argument checks and the pointer look-ups of
-        step_into cost 3.5 us per call on top of the 5.3 us of the launch itself; profiles/tools/gpu_hostpath_probe.py).  The
-        callable keeps the tensors alive; it must not be used after close()."""
+    def _check_step_io(self, actions, obs, reward, absorbing, last, mask):
         B = self.batch
         self._check_io(actions, (B, self.dims['null']), self.dtype, 'actions')
         self._check_io(obs, (B, self.obs_dim), self.dtype, 'obs')
@@ -278,9 +184,51 @@ class BatchedAtacomEnv:
         self._check_io(absorbing, (B,), torch.uint8, 'absorbing')
         self._check_io(last, (B,), torch.uint8, 'last')
         self._check_io(mask, (B,), torch.uint8, 'mask')
+
+    def _launch_step(self, actions, obs, reward, absorbing, last, mask):
+        """atacom_step, or atacom_step_masked when there is a mask, on the caller's current stream."""
+        if mask is None:
+            self._check(self._lib.atacom_step(self._h, _ptr(actions), _ptr(obs), _ptr(reward), _ptr(absorbing), _ptr(last),
+                                              self._stream()))
+        else:
+            self._check(self._lib.atacom_step_masked(self._h, _ptr(mask), _ptr(actions), _ptr(obs), _ptr(reward),
+                                                     _ptr(absorbing), _ptr(last), self._stream()))
+
+    def step(self, actions, mask=None):
+        """mask (optional, [B] bool / uint8): environments with a zero entry sit the call out ON THE DEVICE -- state, step
+        counter and statistics untouched, obs = their current observation, reward 0, flags False."""
+        B = self.batch
+        a = self._as_dev(actions, (B, self.dims['null']))
+        # fresh output tensors written by the kernel itself (the reference returns copies, atacom.py:115); the flags are
+        # 0 / 1 bytes, so the bool tensors are reinterpreting views -- no copy or conversion kernel follows the step
+        obs, reward = self._empty(B, self.obs_dim), self._empty(B)
+        absorbing, last = self._empty(B, dtype=torch.uint8), self._empty(B, dtype=torch.uint8)
+        if mask is not None:
+            mask = mask.view(torch.uint8) if (isinstance(mask, torch.Tensor) and mask.dtype == torch.bool
+                                              and self._on_my_device(mask) and mask.is_contiguous()) \
+                else self._as_dev(mask, (B,), torch.uint8)
+            if tuple(mask.shape) != (B,):
+                raise ValueError("expected a mask of shape (%d,), got %s" % (B, tuple(mask.shape)))
+        self._launch_step(a, obs, reward, absorbing, last, mask)
+        return obs, reward, absorbing.view(torch.bool), {'last': last.view(torch.bool)}
+
+    def step_into(self, actions, obs, reward, absorbing, last=None, mask=None):
+        """Allocation-free variant of step(): caller-owned output tensors (uint8 for the flags).  `mask` (uint8 [B],
+        optional): environments with a zero byte sit the call out on the device (atacom_step_masked)."""
+        self._check_step_io(actions, obs, reward, absorbing, last, mask)
+        self._launch_step(actions, obs, reward, absorbing, last, mask)
+
+    def bind_step(self, actions, obs, reward, absorbing, last=None, mask=None):
+        """step_into() with its arguments validated ONCE: returns a zero-argument callable that launches atacom_step (or
+        atacom_step_masked) on the caller's current stream with these tensors -- for loops that reuse their buffers and are
+        bound by the host (CircularMotion: the kernel runs 4 us, five argument checks and the pointer look-ups of
+        step_into cost 3.5 us per call on top of the 5.3 us of the launch itself; profiles/tools/gpu_hostpath_probe.py).  The
+        callable keeps the tensors alive; it must not be used after close()."""
+        self._check_step_io(actions, obs, reward, absorbing, last, mask)
         keep = (actions, obs, reward, absorbing, last, mask)
         pa, po, pr, pb, pl, pm = [_ptr(t) for t in keep]
-        check, stream = _lib.check, self._stream
+        check, stream = self._check, self._stream
+        # two closures, so that a call does nothing but read the handle, make one C call and check its code
         if mask is None:
             fn = self._lib.atacom_step
 
@@ -303,14 +251,9 @@ class BatchedAtacomEnv:
         """T env steps in one kernel launch.  actions [T, B, k] -> dict(obs, next_obs, reward, absorbing, last)."""
         T = int(actions.shape[0])
         a = self._as_dev(actions, (T, self.batch, self.dims['null']))
-        B, D = self.batch, self.obs_dim
         if out is None:
-            out = {'obs': torch.empty((T, B, D), device=self.device, dtype=self.dtype),
-                   'next_obs': torch.empty((T, B, D), device=self.device, dtype=self.dtype) if want_next_obs else None,
-                   'reward': torch.empty((T, B), device=self.device, dtype=self.dtype),
-                   'absorbing': torch.empty((T, B), device=self.device, dtype=torch.uint8),
-                   'last': torch.empty((T, B), device=self.device, dtype=torch.uint8)}
-        _lib.check(self._lib.atacom_rollout(self._h, T, _ptr(a), _ptr(out['obs']), _ptr(out.get('next_obs')),
+            out = self._rollout_buffers(T, want_next_obs, with_action=False)
+        self._check(self._lib.atacom_rollout(self._h, T, _ptr(a), _ptr(out['obs']), _ptr(out.get('next_obs')),
                                              _ptr(out['reward']), _ptr(out['absorbing']), _ptr(out['last']),
                                              self._stream()))
         out['action'] = a
@@ -320,16 +263,11 @@ class BatchedAtacomEnv:
         """T env steps with the actor MLP evaluated inside the kernel (row N2): one launch for the whole collection
         phase.  `policy` is an MlpPolicy (see below); `noise` [T, B, k] standard-normal draws supplied by the caller
         (None = deterministic mean action).  Returns the same dict as rollout(), 'action' being what the policy drew."""
-        T, B, D, k = int(n_steps), self.batch, self.obs_dim, self.dims['null']
+        T = int(n_steps)
         net = policy.as_struct(self)
-        nz = None if noise is None else self._as_dev(noise, (T, B, k))
-        out = {'obs': torch.empty((T, B, D), device=self.device, dtype=self.dtype),
-               'next_obs': torch.empty((T, B, D), device=self.device, dtype=self.dtype) if want_next_obs else None,
-               'action': torch.empty((T, B, k), device=self.device, dtype=self.dtype),
-               'reward': torch.empty((T, B), device=self.device, dtype=self.dtype),
-               'absorbing': torch.empty((T, B), device=self.device, dtype=torch.uint8),
-               'last': torch.empty((T, B), device=self.device, dtype=torch.uint8)}
-        _lib.check(self._lib.atacom_rollout_mlp(self._h, T, C.byref(net), _ptr(nz), _ptr(out['obs']),
+        nz = None if noise is None else self._as_dev(noise, (T, self.batch, self.dims['null']))
+        out = self._rollout_buffers(T, want_next_obs)
+        self._check(self._lib.atacom_rollout_mlp(self._h, T, C.byref(net), _ptr(nz), _ptr(out['obs']),
                                                  _ptr(out['next_obs']), _ptr(out['action']), _ptr(out['reward']),
                                                  _ptr(out['absorbing']), _ptr(out['last']), self._stream()))
         return out
@@ -341,27 +279,10 @@ class BatchedAtacomEnv:
         evaluated inside the kernel; `noise` [T, B, k] or None) with `n_steps`.  batch_stride > batch pads the env axis
         (ragged shards); the padding rows are zero (filled at allocation, or here when the caller supplies `out`) and never
         written by the kernel."""
-        B, k, F = self.batch, self.dims['null'], self.record_dim
-        if (actions is None) == (policy is None):
-            raise ValueError("give either actions or policy")
-        T = int(actions.shape[0]) if actions is not None else int(n_steps)
-        ld = B if batch_stride is None else int(batch_stride)
-        if out is None:
-            alloc = torch.empty if ld == B else torch.zeros
-            out = alloc((T, ld, F), device=self.device, dtype=self.dtype)
-        elif tuple(out.shape) != (T, ld, F) or not out.is_contiguous() or out.dtype != self.dtype \
-                or not self._on_my_device(out):
-            raise ValueError("out must be a contiguous [%d, %d, %d] tensor of the engine's dtype on %s" % (T, ld, F, self.device))
-        elif ld > B:
-            out[:, B:].zero_()                  # a caller's buffer may hold anything: the padding rows are zero (rollout.py)
-        if actions is not None:
-            a = self._as_dev(actions, (T, B, k))
-            _lib.check(self._lib.atacom_rollout_packed(self._h, T, _ptr(a), None, None, _ptr(out), ld, self._stream()))
-        else:
-            net = policy.as_struct(self)
-            nz = None if noise is None else self._as_dev(noise, (T, B, k))
-            _lib.check(self._lib.atacom_rollout_packed(self._h, T, None, C.byref(net), _ptr(nz), _ptr(out), ld,
-                                                        self._stream()))
+        T, a_ptr, net_ref, noise_ptr, _keep = self._source(actions, policy, n_steps, noise)
+        ld = self.batch if batch_stride is None else int(batch_stride)
+        out = self._packed_out(T, ld, self.record_dim, out)
+        self._check(self._lib.atacom_rollout_packed(self._h, T, a_ptr, net_ref, noise_ptr, _ptr(out), ld, self._stream()))
         return out
 
     def rollout_compact(self, actions=None, policy=None, n_steps=None, noise=None, out=None, batch_stride=None,
@@ -375,53 +296,28 @@ class BatchedAtacomEnv:
         (records, ends) caller buffers of those shapes (ends [ends_capacity, D + 2]); padding rows are zeroed as in
         rollout_packed.  Reads the row count back: synchronises the current stream once.  Raises ValueError when the count
         exceeds the capacity -- the rows past it are lost, and the engine has advanced all the same."""
-        B, k, D = self.batch, self.dims['null'], self.obs_dim
-        Fc = D + k + 3
-        if (actions is None) == (policy is None):
-            raise ValueError("give either actions or policy")
-        T = int(actions.shape[0]) if actions is not None else int(n_steps)
+        B = self.batch
+        _, Fc, E = compact_record_fields(self.obs_dim, self.dims['null'])
+        T, a_ptr, net_ref, noise_ptr, _keep = self._source(actions, policy, n_steps, noise)
         ld = B if batch_stride is None else int(batch_stride)
         cap = max(T - 1, 0) * B if ends_capacity is None else int(ends_capacity)
         if cap < 0:
             raise ValueError("ends_capacity must be >= 0")
-        if out is None:
-            rec = (torch.empty if ld == B else torch.zeros)((T + 1, ld, Fc), device=self.device, dtype=self.dtype)
-            ends = torch.empty((cap, D + 2), device=self.device, dtype=self.dtype)
-        else:
-            rec, ends = out
-            if tuple(rec.shape) != (T + 1, ld, Fc) or not rec.is_contiguous() or rec.dtype != self.dtype \
-                    or not self._on_my_device(rec):
-                raise ValueError("out[0] must be a contiguous [%d, %d, %d] tensor of the engine's dtype on %s"
-                                 % (T + 1, ld, Fc, self.device))
-            if ends.dim() != 2 or ends.shape[0] < cap or ends.shape[1] != D + 2 or not ends.is_contiguous() \
-                    or ends.dtype != self.dtype or not self._on_my_device(ends):
-                raise ValueError("out[1] must be a contiguous [>= %d, %d] tensor of the engine's dtype on %s"
-                                 % (cap, D + 2, self.device))
-            if ld > B:
-                rec[:, B:].zero_()
-        n_ends = torch.empty((1,), device=self.device, dtype=torch.int32)
-        if actions is not None:
-            a = self._as_dev(actions, (T, B, k))
-            _lib.check(self._lib.atacom_rollout_compact(self._h, T, _ptr(a), None, None, _ptr(rec), ld,
-                                                         _ptr(ends) if cap > 0 else None, cap, _ptr(n_ends), self._stream()))
-        else:
-            net = policy.as_struct(self)
-            nz = None if noise is None else self._as_dev(noise, (T, B, k))
-            _lib.check(self._lib.atacom_rollout_compact(self._h, T, None, C.byref(net), _ptr(nz), _ptr(rec), ld,
-                                                         _ptr(ends) if cap > 0 else None, cap, _ptr(n_ends), self._stream()))
+        rec, ends = (None, self._empty(cap, E)) if out is None else out
+        rec = self._packed_out(T + 1, ld, Fc, rec, 'out[0]')
+        if ends.dim() != 2 or ends.shape[0] < cap or ends.shape[1] != E or not ends.is_contiguous() \
+                or ends.dtype != self.dtype or not self._on_my_device(ends):
+            raise ValueError("out[1] must be a contiguous [>= %d, %d] tensor of the engine's dtype on %s"
+                             % (cap, E, self.device))
+        n_ends = self._empty(1, dtype=torch.int32)
+        self._check(self._lib.atacom_rollout_compact(self._h, T, a_ptr, net_ref, noise_ptr, _ptr(rec), ld,
+                                                     _ptr(ends) if cap > 0 else None, cap, _ptr(n_ends), self._stream()))
         n = int(n_ends.item())
         if n > cap:
             raise ValueError("rollout_compact: %d episode-end rows, capacity %d -- the rows past the capacity were not written. "
                              "The engine has advanced: take a snapshot() before the call to retry it with a larger "
                              "ends_capacity" % (n, cap))
         return rec, ends[:n], n
-
-    def unpack_records(self, rec):
-        """Views into packed records [..., record_dim] (no copy)."""
-        D, k = self.obs_dim, self.dims['null']
-        return {'obs': rec[..., :D], 'action': rec[..., D:D + k], 'reward': rec[..., D + k],
-                'next_obs': rec[..., D + k + 1:2 * D + k + 1], 'absorbing': rec[..., 2 * D + k + 1] > 0.5,
-                'last': rec[..., 2 * D + k + 2] > 0.5}
 
     def _lanes(self):
         a, b = C.c_int32(0), C.c_int32(0)
@@ -446,9 +342,6 @@ class BatchedAtacomEnv:
         a = C.c_int32(0)
         _lib.check(self._lib.atacom_get_policy_lanes(self._h, C.byref(a)))
         return int(a.value)
-
-    def _on_my_device(self, t):
-        return t.device.type == 'cuda' and t.device.index == self._dev_index
 
     def snapshot(self, out=None):
         """Checkpoint of the WHOLE persistent state (atacom_snapshot_save): what get_state() returns plus the stored initial
@@ -517,18 +410,6 @@ class BatchedAtacomEnv:
         a = self._as_dev(fv, (self.batch, 3 + self.dims['q']))
         _lib.check(self._lib.atacom_set_filter_state(self._h, _ptr(a), self._stream()))
 
-    def close(self):
-        if getattr(self, '_h', None) is not None and self._h:
-            self._lib.atacom_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
 class GraphedRollout:
     """A T-step collection loop -- observe, ARBITRARY torch policy, env step -- captured ONCE in a HIP graph and replayed
     with one host call per collection phase.
@@ -548,15 +429,9 @@ class GraphedRollout:
 
     def __init__(self, env, policy, n_steps, warmup=2):
         self.env, self.T = env, int(n_steps)
-        T, B, D, k = self.T, env.batch, env.obs_dim, env.dims['null']
-        dev, dt = env.device, env.dtype
-        self.out = {'obs': torch.empty((T, B, D), device=dev, dtype=dt),
-                    'action': torch.empty((T, B, k), device=dev, dtype=dt),
-                    'reward': torch.empty((T, B), device=dev, dtype=dt),
-                    'next_obs': torch.empty((T, B, D), device=dev, dtype=dt),
-                    'absorbing': torch.empty((T, B), device=dev, dtype=torch.uint8),
-                    'last': torch.empty((T, B), device=dev, dtype=torch.uint8)}
-        self._none = torch.zeros((B,), device=dev, dtype=torch.uint8)       # reset mask selecting nobody = "observe"
+        T, dev = self.T, env.device
+        self.out = env._rollout_buffers(T)
+        self._none = torch.zeros((env.batch,), device=dev, dtype=torch.uint8)   # reset mask selecting nobody = "observe"
         saved = env.snapshot()             # everything: state, statistics, episode counters, servo joints
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -741,23 +616,28 @@ class MlpPolicy:
 
 
 # ---------------------------------------------------------------------- stand-alone primitives
+@contextlib.contextmanager
+def _primitive(ref):
+    """(library, dtype code of `ref`, its device's current stream) for a stand-alone primitive; ref's device is current
+    inside the block."""
+    with torch.cuda.device(ref.device):
+        yield _lib.load(), _DTYPES[ref.dtype], C.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream)
+
+
 def nullspace(env, Jc, rhs=None, tol=0.05, lanes_per_env=1):
     """Batched pinv_null + rref on the GPU (null_space_coordinate.py:8-26,40-79).
     Jc [n, c, c+k] (torch, on a ROCm device).  Returns (x = Jc^+ rhs, null basis, rref(null, tol))."""
-    lib = _lib.load()
     env_id = _ENV_IDS[env] if isinstance(env, str) else int(env)
     d = _lib.get_dims(env_id)
     c, k = d.n_f + d.n_g, d.n_null
     n = Jc.shape[0]
     assert Jc.is_cuda and tuple(Jc.shape) == (n, c, c + k)
     Jc = Jc.contiguous()
-    dt = {torch.float32: _lib.F32, torch.float64: _lib.F64}[Jc.dtype]
     rhs = torch.zeros((n, c), device=Jc.device, dtype=Jc.dtype) if rhs is None else rhs.contiguous()
     x = torch.empty((n, c + k), device=Jc.device, dtype=Jc.dtype)
     nb = torch.empty((n, c + k, k), device=Jc.device, dtype=Jc.dtype)
     rr = torch.empty((n, c + k, k), device=Jc.device, dtype=Jc.dtype)
-    stream = C.c_void_p(torch.cuda.current_stream(Jc.device).cuda_stream)
-    with torch.cuda.device(Jc.device):
+    with _primitive(Jc) as (lib, dt, stream):
         _lib.check(lib.atacom_nullspace(env_id, dt, int(lanes_per_env), n, _ptr(Jc), _ptr(rhs), float(tol), _ptr(x), _ptr(nb), _ptr(rr),
                                         stream))
     return x, nb, rr
@@ -765,19 +645,17 @@ def nullspace(env, Jc, rhs=None, tol=0.05, lanes_per_env=1):
 
 def constraint_terms(env, q, dq, bias_mode='reference'):
     """fun / J / b callables of an environment evaluated on the GPU for q, dq [n, dim_q]."""
-    lib = _lib.load()
     env_id = _ENV_IDS[env] if isinstance(env, str) else int(env)
     d = _lib.get_dims(env_id)
     cfg = _lib.default_config(env_id)
-    cfg.dtype = {torch.float32: _lib.F32, torch.float64: _lib.F64}[q.dtype]
     cfg.bias_mode = {'reference': 0, 'exact': 1}[bias_mode]
     n, c = q.shape[0], d.n_f + d.n_g
     q, dq = q.contiguous(), dq.contiguous()
     fun = torch.empty((n, c), device=q.device, dtype=q.dtype)
     J = torch.empty((n, c, d.dim_q), device=q.device, dtype=q.dtype)
     b = torch.empty((n, c), device=q.device, dtype=q.dtype)
-    stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-    with torch.cuda.device(q.device):
+    with _primitive(q) as (lib, dt, stream):
+        cfg.dtype = dt
         _lib.check(lib.atacom_constraint_terms(C.byref(cfg), n, _ptr(q), _ptr(dq), _ptr(fun), _ptr(J), _ptr(b), stream))
     return fun, J, b
 
@@ -799,7 +677,6 @@ def canonical_mu(env, A, s, y, alpha, tol=0.05):
     Contract: the entries of A that the environment's constraint Jacobian leaves STRUCTURALLY zero (planar / iiwa joint-limit
     rows off their diagonal; iiwa row 4, joints 3..6) are not read -- a general matrix is treated as having zeros there
     (include/atacom_hip.h)."""
-    lib = _lib.load()
     env_id = _ENV_IDS[env] if isinstance(env, str) else int(env)
     d = _lib.get_dims(env_id)
     n, c, nq, ng, k = A.shape[0], d.n_f + d.n_g, d.dim_q, d.n_g, d.dim_q - d.n_f
@@ -808,10 +685,8 @@ def canonical_mu(env, A, s, y, alpha, tol=0.05):
     _check_same(A, (n, c), y=y)
     _check_same(A, (n, k), alpha=alpha)
     A, s, y, alpha = A.contiguous(), s.contiguous(), y.contiguous(), alpha.contiguous()
-    dt = {torch.float32: _lib.F32, torch.float64: _lib.F64}[A.dtype]
     mu = torch.empty((n, nq + ng), device=A.device, dtype=A.dtype)
-    stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
-    with torch.cuda.device(A.device):
+    with _primitive(A) as (lib, dt, stream):
         _lib.check(lib.atacom_canonical_mu(env_id, dt, n, _ptr(A), _ptr(s), _ptr(y), _ptr(alpha), float(tol), _ptr(mu), stream))
     return mu
 
@@ -820,15 +695,12 @@ def inverse_dynamics(q, dq, ddq, want_mass_matrix=False):
     """Row N4 primitive: tau = M(q) ddq + C(q, dq) dq + g(q) of the nine-joint iiwa + striker chain on the GPU
     (what the reference asks PyBullet for, iiwa_hit_atacom.py:58-63).  q, dq, ddq [n, 9]; returns tau [n, 9]
     (and M [n, 9, 9])."""
-    lib = _lib.load()
     n = q.shape[0]
     _check_same(q, (n, 9), q=q, dq=dq, ddq=ddq)
     q, dq, ddq = q.contiguous(), dq.contiguous(), ddq.contiguous()
-    dt = {torch.float32: _lib.F32, torch.float64: _lib.F64}[q.dtype]
     tau = torch.empty((n, 9), device=q.device, dtype=q.dtype)
     M = torch.empty((n, 9, 9), device=q.device, dtype=q.dtype) if want_mass_matrix else None
-    stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-    with torch.cuda.device(q.device):
+    with _primitive(q) as (lib, dt, stream):
         _lib.check(lib.atacom_inverse_dynamics(dt, n, _ptr(q), _ptr(dq), _ptr(ddq), _ptr(tau), _ptr(M), stream))
     return (tau, M) if want_mass_matrix else tau
 
@@ -836,7 +708,6 @@ def inverse_dynamics(q, dq, ddq, want_mass_matrix=False):
 def forward_dynamics(q, dq, tau6, ddq_aux=None, damping=True):
     """Row N4 primitive: accelerations [n, 6] of the controlled joints under torques tau6 [n, 6]; the servo joints follow
     ddq_aux [n, 3] (None = at rest)."""
-    lib = _lib.load()
     n = q.shape[0]
     _check_same(q, (n, 9), q=q, dq=dq)
     _check_same(q, (n, 6), tau6=tau6)
@@ -844,10 +715,8 @@ def forward_dynamics(q, dq, tau6, ddq_aux=None, damping=True):
         _check_same(q, (n, 3), ddq_aux=ddq_aux)
     q, dq, tau6 = q.contiguous(), dq.contiguous(), tau6.contiguous()
     aux = None if ddq_aux is None else ddq_aux.contiguous()
-    dt = {torch.float32: _lib.F32, torch.float64: _lib.F64}[q.dtype]
     out = torch.empty((n, 6), device=q.device, dtype=q.dtype)
-    stream = C.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-    with torch.cuda.device(q.device):
+    with _primitive(q) as (lib, dt, stream):
         _lib.check(lib.atacom_forward_dynamics(dt, n, _ptr(q), _ptr(dq), _ptr(tau6), _ptr(aux), int(bool(damping)), _ptr(out),
                                                stream))
     return out

@@ -11,6 +11,7 @@ They are thin: one BatchedAtacomEnv with batch = 1 (or `n_envs` > 1 for a vector
 import numpy as np
 import torch
 
+from ._device_env import step_to_host
 from .engine import BatchedAtacomEnv
 
 DEFEND_START_RANGE = np.array([[0.25, 0.65], [-0.4, 0.4]])   # mushroom_rl AirHockeyDefend.start_range [upstream]
@@ -44,12 +45,8 @@ class _Facade:
 
     def step(self, action):
         """atacom.py:106-115: returns (state copy, float reward, bool absorbing, {})."""
-        a = np.asarray(action, dtype=np.float64).reshape(1, -1)
-        obs, r, ab, _ = self._engine.step(a)
-        # one device -> host transfer (and one synchronisation) per step: observation, reward and flag travel together
-        host = torch.cat([obs[0], r, ab.to(obs.dtype)]).cpu().numpy().astype(np.float64)
-        self.state = host[:-2].copy()
-        return self.state.copy(), float(host[-2]), bool(host[-1] != 0.0), {}
+        self.state, reward, absorbing = step_to_host(self._engine, action)
+        return self.state.copy(), reward, absorbing, {}
 
     def get_constraints_logs(self):
         return self._engine.get_constraints_logs()

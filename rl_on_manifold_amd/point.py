@@ -18,23 +18,21 @@ import numpy as np
 import torch
 
 from . import _lib_point, _lib_point_policy
-from .engine import _ptr, _raw_stream
+from ._device_env import DeviceEnv, _ptr, step_to_host
+from .rollout import record_fields
 from .spaces import Box, MDPInfo
 
 
-class BatchedPointReachEnv:
+class BatchedPointReachEnv(DeviceEnv):
+    _destroy = 'atacom_point_destroy'
+
     def __init__(self, batch, n_objects=4, random_walk=True, time_step=0.01, horizon=1000, gamma=0.99, seed=0,
                  auto_reset=True, device='cuda:0', dtype=torch.float32):
         """The state is zero until the first reset(): like the reference's constructor, this one does not reset (the
         circle centres of random_walk=False are those of the FIRST reset, for the life of the object)."""
         lib = _lib_point.load()
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise ValueError("the engine runs on a ROCm device ('cuda:N'); there is no CPU path")
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        if dtype not in (torch.float32, torch.float64):
-            raise ValueError('dtype must be torch.float32 or torch.float64')
-        self.dtype = dtype
+        self._init_device(device, dtype, _lib_point.check,
+                          ValueError("the engine runs on a ROCm device ('cuda:N'); there is no CPU path"))
         cfg = _lib_point.default_config()
         cfg.batch, cfg.n_objects, cfg.random_walk = int(batch), int(n_objects), int(bool(random_walk))
         cfg.dtype = _lib_point.F32 if dtype == torch.float32 else _lib_point.F64
@@ -44,7 +42,6 @@ class BatchedPointReachEnv:
         n = self.n_objects
         self.obs_dim, self.state_dim = 4 * (1 + n), 7 * n + 8
         self.dims = {'q': 2, 'f': 0, 'g': n, 'null': 2, 'c': n}
-        self._h = None
         h = C.c_void_p()
         _lib_point.check(lib.atacom_point_create(C.byref(cfg), self._dev_index, C.byref(h)))
         self._h, self._lib = h, lib
@@ -61,26 +58,6 @@ class BatchedPointReachEnv:
         """Re-keys the device generator from the next call on."""
         self.cfg.seed = int(seed) & 0x7fffffff
         _lib_point.check(self._lib.atacom_point_set_seed(self._h, self.cfg.seed))
-
-    def render(self):
-        pass
-
-    def stop(self):
-        pass
-
-    def _stream(self):
-        if _raw_stream is not None:
-            return _raw_stream(self._dev_index)
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _as_dev(self, x, shape, dtype=None):
-        t = torch.as_tensor(x, dtype=dtype or self.dtype, device=self.device)
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
-        return t.contiguous()
-
-    def _empty(self, *shape, dtype=None):
-        return torch.empty(shape, device=self.device, dtype=dtype or self.dtype)
 
     def reset(self, mask=None, draws=None):
         """Reset the masked environments (all if mask is None).  draws (optional) [B, n_objects, 2]: the obstacle
@@ -103,16 +80,6 @@ class BatchedPointReachEnv:
                                                      _ptr(last), self._stream()))
         return obs, reward, absorbing.view(torch.bool), {'last': last.view(torch.bool)}
 
-    def _check_io(self, t, shape, dtype, what):
-        if t is None:
-            return
-        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or \
-                (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self._dev_index:
-            raise ValueError("%s must be a torch tensor on %s" % (what, self.device))
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s (got %s, %s)"
-                             % (what, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-
     def step_into(self, actions, obs, reward, absorbing, last=None, draws=None):
         """Allocation-free variant of step(): caller-owned output tensors (uint8 for the flags)."""
         B = self.batch
@@ -129,26 +96,21 @@ class BatchedPointReachEnv:
         """T env steps in one kernel launch.  actions [T, B, 2], draws (optional) [T, B, n_objects, 2]
         -> dict(obs, next_obs, reward, absorbing, last, action), the layout of BatchedAtacomEnv.rollout."""
         T = int(actions.shape[0])
-        B, D = self.batch, self.obs_dim
+        B = self.batch
         a = self._as_dev(actions, (T, B, 2))
         d = None if draws is None else self._as_dev(draws, (T, B, self.n_objects, 2))
         if out is None:
-            out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D) if want_next_obs else None,
-                   'reward': self._empty(T, B), 'absorbing': self._empty(T, B, dtype=torch.uint8),
-                   'last': self._empty(T, B, dtype=torch.uint8)}
+            out = self._rollout_buffers(T, want_next_obs, with_action=False)
         _lib_point.check(self._lib.atacom_point_rollout(self._h, T, _ptr(a), _ptr(d), _ptr(out['obs']),
                                                         _ptr(out.get('next_obs')), _ptr(out['reward']),
                                                         _ptr(out['absorbing']), _ptr(out['last']), self._stream()))
         out['action'] = a
         return out
 
-    def _on_my_device(self, t):
-        return t.device.type == 'cuda' and t.device.index == self._dev_index
-
     @property
     def record_dim(self):
         """Values of one packed record: [obs | action(2) | reward | next_obs | absorbing | last]."""
-        return 2 * self.obs_dim + 5
+        return record_fields(self.obs_dim, 2)[1]
 
     def _policy_lib(self):
         if getattr(self, '_plib', None) is None:
@@ -166,13 +128,11 @@ class BatchedPointReachEnv:
           policy.forward + step, n_steps launches of each, starting from the current observation (`noise` and `draws` are not
           taken there: the callable owns its exploration)."""
         if hasattr(policy, 'as_struct'):
-            T, B, D, n = int(n_steps), self.batch, self.obs_dim, self.n_objects
+            T, B = int(n_steps), self.batch
             net = policy.as_struct(self)
             nz = None if noise is None else self._as_dev(noise, (T, B, 2))
-            d = None if draws is None else self._as_dev(draws, (T, B, n, 2))
-            out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D) if want_next_obs else None,
-                   'action': self._empty(T, B, 2), 'reward': self._empty(T, B),
-                   'absorbing': self._empty(T, B, dtype=torch.uint8), 'last': self._empty(T, B, dtype=torch.uint8)}
+            d = None if draws is None else self._as_dev(draws, (T, B, self.n_objects, 2))
+            out = self._rollout_buffers(T, want_next_obs)
             _lib_point_policy.check(self._policy_lib().atacom_point_policy_rollout(
                 self._h, T, C.byref(net), _ptr(nz), _ptr(d), _ptr(out['obs']), _ptr(out['next_obs']), _ptr(out['action']),
                 _ptr(out['reward']), _ptr(out['absorbing']), _ptr(out['last']), self._stream()))
@@ -180,10 +140,8 @@ class BatchedPointReachEnv:
         if noise is not None or draws is not None:
             raise ValueError("noise / draws go with an MlpPolicy (the fused kernel); a plain callable runs the host loop and "
                              "owns its exploration")
-        T, B, D = int(n_steps), self.batch, self.obs_dim
-        out = {'obs': self._empty(T, B, D), 'next_obs': self._empty(T, B, D), 'action': self._empty(T, B, 2),
-               'reward': self._empty(T, B), 'absorbing': self._empty(T, B, dtype=torch.uint8),
-               'last': self._empty(T, B, dtype=torch.uint8)}
+        T, D = int(n_steps), self.obs_dim
+        out = self._rollout_buffers(T)
         fwd = policy.forward if hasattr(policy, 'forward') else policy
         obs = self.get_state()[:, :D].contiguous()
         with torch.no_grad():
@@ -202,40 +160,15 @@ class BatchedPointReachEnv:
         evaluated inside the kernel; `noise` [T, B, 2] or None) with `n_steps`; `draws` as in rollout_policy.  batch_stride >
         batch pads the env axis (ragged shards); the padding rows are zero (filled at allocation, or here when the caller
         supplies `out`) and never written by the kernel."""
-        B, n, F = self.batch, self.n_objects, self.record_dim
-        if (actions is None) == (policy is None):
-            raise ValueError("give either actions or policy")
-        T = int(actions.shape[0]) if actions is not None else int(n_steps)
-        ld = B if batch_stride is None else int(batch_stride)
-        if out is None:
-            alloc = torch.empty if ld == B else torch.zeros
-            out = alloc((T, ld, F), device=self.device, dtype=self.dtype)
-        elif tuple(out.shape) != (T, ld, F) or not out.is_contiguous() or out.dtype != self.dtype \
-                or not self._on_my_device(out):
-            raise ValueError("out must be a contiguous [%d, %d, %d] tensor of the engine's dtype on %s" % (T, ld, F, self.device))
-        elif ld > B:
-            out[:, B:].zero_()                  # a caller's buffer may hold anything: the padding rows are zero (rollout.py)
-        d = None if draws is None else self._as_dev(draws, (T, B, n, 2))
-        lib = self._policy_lib()
-        if actions is not None:
-            a = self._as_dev(actions, (T, B, 2))
-            _lib_point_policy.check(lib.atacom_point_policy_rollout_packed(self._h, T, _ptr(a), None, None, _ptr(d), _ptr(out),
-                                                                           ld, self._stream()))
-        else:
-            if not hasattr(policy, 'as_struct'):
-                raise ValueError("rollout_packed takes an MlpPolicy (as_struct); a plain callable goes through rollout_policy")
-            net = policy.as_struct(self)
-            nz = None if noise is None else self._as_dev(noise, (T, B, 2))
-            _lib_point_policy.check(lib.atacom_point_policy_rollout_packed(self._h, T, None, C.byref(net), _ptr(nz), _ptr(d),
-                                                                           _ptr(out), ld, self._stream()))
+        if actions is None and policy is not None and not hasattr(policy, 'as_struct'):
+            raise ValueError("rollout_packed takes an MlpPolicy (as_struct); a plain callable goes through rollout_policy")
+        T, a_ptr, net_ref, noise_ptr, _keep = self._source(actions, policy, n_steps, noise)
+        ld = self.batch if batch_stride is None else int(batch_stride)
+        out = self._packed_out(T, ld, self.record_dim, out)
+        d = None if draws is None else self._as_dev(draws, (T, self.batch, self.n_objects, 2))
+        _lib_point_policy.check(self._policy_lib().atacom_point_policy_rollout_packed(
+            self._h, T, a_ptr, net_ref, noise_ptr, _ptr(d), _ptr(out), ld, self._stream()))
         return out
-
-    def unpack_records(self, rec):
-        """Views into packed records [..., record_dim] (no copy)."""
-        D, k = self.obs_dim, 2
-        return {'obs': rec[..., :D], 'action': rec[..., D:D + k], 'reward': rec[..., D + k],
-                'next_obs': rec[..., D + k + 1:2 * D + k + 1], 'absorbing': rec[..., 2 * D + k + 1] > 0.5,
-                'last': rec[..., 2 * D + k + 2] > 0.5}
 
     def get_constraints_logs(self, clear=True):
         """(c_avg, c_max, c_dq_max) over every step of every environment since the last clear; c_dq_max is the
@@ -253,17 +186,6 @@ class BatchedPointReachEnv:
     def set_state(self, state):
         st = self._as_dev(state, (self.batch, self.state_dim))
         _lib_point.check(self._lib.atacom_point_set_state(self._h, _ptr(st), self._stream()))
-
-    def close(self):
-        if getattr(self, '_h', None):
-            self._lib.atacom_point_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 class PointReachAtacom:
@@ -304,12 +226,9 @@ class PointReachAtacom:
         return self.state.copy()
 
     def step(self, action, draws=None):
-        a = np.asarray(action, dtype=np.float64).reshape(1, 2)
         d = None if draws is None else np.asarray(draws, dtype=np.float64).reshape(1, self.n_objects, 2)
-        obs, r, ab, _ = self._engine.step(a, draws=d)
-        host = torch.cat([obs[0], r, ab.to(obs.dtype)]).cpu().numpy().astype(np.float64)
-        self.state = host[:-2].copy()
-        return self.state.copy(), float(host[-2]), bool(host[-1] != 0.0), {}
+        self.state, reward, absorbing = step_to_host(self._engine, action, draws=d)
+        return self.state.copy(), reward, absorbing, {}
 
     def get_constraints_logs(self):
         return self._engine.get_constraints_logs()

@@ -39,6 +39,36 @@ def shard_bounds(global_batch, world_size, rank):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def record_fields(D, k):
+    """(fields, F): where each field of the full packed record [obs | action | reward | next_obs | absorbing | last] sits --
+    a slice or an index into the last axis, listed in record order -- and the record's length F = 2 D + k + 3.  Order and
+    widths are the ABI of `Record<E>` (and, below, of `RecordCompact<E>`) in csrc/atacom_kernels.h: this is the one place
+    the Python side spells them out."""
+    o = D + k
+    return {'obs': slice(0, D), 'action': slice(D, o), 'reward': o, 'next_obs': slice(o + 1, o + 1 + D),
+            'absorbing': o + 1 + D, 'last': o + 2 + D}, 2 * D + k + 3
+
+
+def compact_record_fields(D, k):
+    """(fields, Fc, E) of the compact format: the record [obs | action | reward | absorbing | last] of Fc = D + k + 3 floats
+    and the length E = D + 2 of an exception row [t, b, terminal obs]."""
+    o = D + k
+    return {'obs': slice(0, D), 'action': slice(D, o), 'reward': o, 'absorbing': o + 1, 'last': o + 2}, o + 3, D + 2
+
+
+def unpack_fields(rec, fields):
+    """Views (no copy) of `fields` into records [..., F]; the two flags as bool."""
+    out = {name: rec[..., ix] for name, ix in fields.items()}
+    out['absorbing'], out['last'] = out['absorbing'] > 0.5, out['last'] > 0.5
+    return out
+
+
+def pack_fields(rec, fields, values):
+    """Write `values` (one array per field, in record order; flags of any dtype) into the fields of rec [..., F]."""
+    for ix, v in zip(fields.values(), values):
+        rec[..., ix] = v.to(rec.dtype)
+
+
 class RecordLayout:
     """The shard-major layout of a gathered collection, [W, T, Bm, F] with F = 2 D + k + 3 packed floats per (step, env):
     [obs | action | reward | next_obs | absorbing | last].  Pure index arithmetic -- usable without a process group
@@ -49,14 +79,11 @@ class RecordLayout:
         self.world = len(self.sizes)
         self.Bm = max(self.sizes)
         self.D, self.k = int(obs_dim), int(n_null)
-        self.F = 2 * self.D + self.k + 3
+        self.fields, self.F = record_fields(self.D, self.k)
 
     def unpack(self, g):
         """Views (no copy) into records [..., F]."""
-        D, k = self.D, self.k
-        return {'obs': g[..., :D], 'action': g[..., D:D + k], 'reward': g[..., D + k],
-                'next_obs': g[..., D + k + 1:2 * D + k + 1], 'absorbing': g[..., 2 * D + k + 1] > 0.5,
-                'last': g[..., 2 * D + k + 2] > 0.5}
+        return unpack_fields(g, self.fields)
 
     def time_major(self, data):
         """[W, T, Bm, ...] -> [T, B_global, ...] with rank r's envs in block shard_bounds(global_batch, W, r); the
@@ -79,8 +106,7 @@ class CompactRecordLayout(RecordLayout):
     def __init__(self, sizes, obs_dim, n_null, n_steps):
         super().__init__(sizes, obs_dim, n_null)
         self.T = int(n_steps)
-        self.Fc = self.D + self.k + 3
-        self.E = self.D + 2                                   # floats per exception row
+        self.compact_fields, self.Fc, self.E = compact_record_fields(self.D, self.k)   # E: floats per exception row
         self.record_numel = (self.T + 1) * self.Bm * self.Fc  # elements of one rank's records
 
     def unpack(self, records, ends=None, n_ends=None):
@@ -94,11 +120,12 @@ class CompactRecordLayout(RecordLayout):
             records = records.unsqueeze(0)
             ends = None if ends is None else ends.unsqueeze(0)
             n_ends = None if n_ends is None else [n_ends]
-        D, k, T = self.D, self.k, self.T
+        T = self.T
         if records.dim() != 4 or records.shape[1] != T + 1 or records.shape[3] != self.Fc:
             raise ValueError("compact records must be [W, %d, Bm, %d], got %s" % (T + 1, self.Fc, tuple(records.shape)))
         body = records[:, :T]
-        nobs = records[:, 1:, :, :D].clone()                 # obs of the next step; the tail row closes the last step
+        # obs of the next step; the tail row closes the last step
+        nobs = records[:, 1:][..., self.compact_fields['obs']].clone()
         if ends is not None and ends.shape[1] > 0:
             W, M = ends.shape[0], ends.shape[1]
             if ends.shape[2] != self.E:
@@ -115,8 +142,8 @@ class CompactRecordLayout(RecordLayout):
                 if bool(bad.any()):
                     raise ValueError("an exception row names a (t, b) outside the [%d, %d] records" % (T, records.shape[2]))
                 nobs[rank.to(nobs.device), t.to(nobs.device), b.to(nobs.device)] = rows[:, 2:].to(nobs.device)
-        out = {'obs': body[..., :D], 'action': body[..., D:D + k], 'reward': body[..., D + k], 'next_obs': nobs,
-               'absorbing': body[..., D + k + 1] > 0.5, 'last': body[..., D + k + 2] > 0.5}
+        out = unpack_fields(body, self.compact_fields)
+        out = {name: nobs if name == 'next_obs' else out[name] for name in self.fields}      # the full format's order
         return {key: v[0] for key, v in out.items()} if one else out
 
 
@@ -186,9 +213,9 @@ class RolloutCollector:
         self.Bm = max(self.sizes)                 # env-axis length of every rank's send buffer
         self.k = env.dims['null']
         self.D = env.obs_dim
-        self.F = 2 * self.D + self.k + 3          # obs, action, reward, next_obs, absorbing, last
-        self.Fc = self.D + self.k + 3             # the compact record: the same minus next_obs
         self.layout = RecordLayout(self.sizes, self.D, self.k)
+        self.F = self.layout.F                    # obs, action, reward, next_obs, absorbing, last
+        self.Fc = compact_record_fields(self.D, self.k)[1]   # the compact record: the same minus next_obs
         self._recv = None
         self._recv_flat = None
         self.mappings = self._agree_on_mappings()
@@ -253,18 +280,13 @@ class RolloutCollector:
             return env.rollout_packed(policy=policy, n_steps=n_steps, noise=noise, out=out, batch_stride=self.Bm)
         # engines without the packed kernel (the CPU test double) and host-side policies: pack here
         B = env.batch
-        obs, act, rew, nobs, ab, last = self._host_rollout(n_steps, actions, policy)
+        rollout = self._host_rollout(n_steps, actions, policy)
+        obs = rollout[0]
         T = obs.shape[0]
         buf = torch.zeros((T, self.Bm, self.F), device=obs.device, dtype=obs.dtype) if out is None else out
         if out is not None and self.Bm > B:
             out[:, B:] = 0                         # a caller's buffer may hold anything: the padding rows are zero
-        D, k = self.D, self.k
-        buf[:, :B, :D] = obs
-        buf[:, :B, D:D + k] = act
-        buf[:, :B, D + k] = rew
-        buf[:, :B, D + k + 1:2 * D + k + 1] = nobs
-        buf[:, :B, 2 * D + k + 1] = ab.to(obs.dtype)
-        buf[:, :B, 2 * D + k + 2] = last.to(obs.dtype)
+        pack_fields(buf[:, :B], self.layout.fields, rollout)
         return buf
 
     def _host_rollout(self, n_steps, actions, policy):
@@ -325,19 +347,15 @@ class RolloutCollector:
             return sh
         # engines without the compact kernel and host-side policies: pack here, listing every last row before the final
         # step (a superset of the auto-resets; the reconstruction is the same for any superset)
-        B, D, k = env.batch, self.D, self.k
+        B = env.batch
         obs, act, rew, nobs, ab, last = self._host_rollout(T, actions, policy)
         if flat is None:
             flat = torch.empty((need,), device=obs.device, dtype=obs.dtype)
         sh = CompactShard(flat, lay, cap)
         rec = sh.records
         rec.zero_()
-        rec[:T, :B, :D] = obs
-        rec[:T, :B, D:D + k] = act
-        rec[:T, :B, D + k] = rew
-        rec[:T, :B, D + k + 1] = ab.to(obs.dtype)
-        rec[:T, :B, D + k + 2] = last.to(obs.dtype)
-        rec[T, :B, :D] = nobs[T - 1]
+        pack_fields(rec[:T, :B], lay.compact_fields, (obs, act, rew, ab, last))
+        rec[T, :B, lay.compact_fields['obs']] = nobs[T - 1]
         tb = torch.nonzero(last[:T - 1].to(torch.bool))           # [n, 2] = (t, b)
         n = int(tb.shape[0])
         if n:

@@ -107,3 +107,106 @@ def test_bench_dump_outputs_types_and_cap(tmp_path, monkeypatch):
         if n != 'sample_rows.npy':
             assert np.array_equal(a, arrays[n[:-4]][rows.astype(np.int64)].astype(a.dtype))
     assert payload <= 20000
+
+
+# ------------------------------------------------------------------ the shared host layer of the device environments
+def _same_view(a, b):
+    return a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+
+
+class _Stub:
+    """What the shared methods read, without a GPU or a library."""
+    def __init__(self, B=3, D=4, k=2):
+        self.batch, self.obs_dim, self.dims = B, D, {'null': k}
+        self.device, self.dtype = torch.device('cpu'), torch.float64
+
+    def _on_my_device(self, t):
+        return t.device == self.device
+
+
+@settings(max_examples=50, deadline=None)
+@given(st.integers(1, 9), st.integers(1, 6), st.integers(0, 10 ** 6))
+def test_record_layout_has_one_definition(D, k, seed):
+    """The field slices of rollout.record_fields are the views RecordLayout.unpack and both engines' unpack_records return."""
+    from rl_on_manifold_amd.rollout import RecordLayout, compact_record_fields, record_fields
+    from rl_on_manifold_amd.engine import BatchedAtacomEnv
+    from rl_on_manifold_amd.point import BatchedPointReachEnv
+    fields, F = record_fields(D, k)
+    _, Fc, E = compact_record_fields(D, k)
+    assert F == 2 * D + k + 3 and Fc == D + k + 3 and E == D + 2
+    rec = torch.rand((2, 3, F), generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+    stub = _Stub(3, D, k)
+    got = (RecordLayout([3], D, k).unpack(rec), BatchedAtacomEnv.unpack_records(stub, rec),
+           BatchedPointReachEnv.unpack_records(stub, rec))
+    for name in ('obs', 'action', 'reward', 'next_obs'):
+        assert all(_same_view(g[name], rec[..., fields[name]]) for g in got), name
+    for name in ('absorbing', 'last'):
+        assert all(g[name].dtype == torch.bool and torch.equal(g[name], rec[..., fields[name]] > 0.5) for g in got), name
+    # the fields tile the record in the order [obs | action | reward | next_obs | absorbing | last]
+    cover = torch.cat([torch.arange(F)[ix].reshape(-1) for ix in fields.values()])
+    assert list(fields) == ['obs', 'action', 'reward', 'next_obs', 'absorbing', 'last'] and torch.equal(cover, torch.arange(F))
+
+
+def test_compact_layout_rebuilds_a_hand_built_dataset():
+    """T = 3, B = 2, D = 2, k = 1: records [T + 1, B, Fc = 6] and two exception rows against the dataset written out by hand."""
+    from rl_on_manifold_amd.rollout import CompactRecordLayout
+    T, B, D, k = 3, 2, 2, 1
+    f64 = torch.float64
+    #                        obs         action reward absorbing last
+    rec = torch.tensor([[[1.0, 2.0, 0.1, 10.0, 0.0, 1.0], [3.0, 4.0, 0.2, 20.0, 1.0, 1.0]],          # t = 0: both envs end
+                        [[5.0, 6.0, 0.3, 30.0, 0.0, 0.0], [7.0, 8.0, 0.4, 40.0, 0.0, 0.0]],          # t = 1
+                        [[9.0, 10.0, 0.5, 50.0, 0.0, 0.0], [11.0, 12.0, 0.6, 60.0, 0.0, 1.0]],       # t = 2
+                        [[13.0, 14.0, 0.0, 0.0, 0.0, 0.0], [15.0, 16.0, 0.0, 0.0, 0.0, 0.0]]], dtype=f64)   # the tail
+    ends = torch.tensor([[0.0, 1.0, -3.0, -4.0], [0.0, 0.0, -1.0, -2.0]], dtype=f64)               # [t, b, terminal obs]
+    lay = CompactRecordLayout([B], D, k, T)
+    assert (lay.Fc, lay.E) == (6, 4) and rec.shape == (T + 1, B, lay.Fc)
+    got = lay.unpack(rec, ends)
+    want = {'obs': [[[1, 2], [3, 4]], [[5, 6], [7, 8]], [[9, 10], [11, 12]]],
+            'action': [[[0.1], [0.2]], [[0.3], [0.4]], [[0.5], [0.6]]],
+            'reward': [[10, 20], [30, 40], [50, 60]],
+            'next_obs': [[[-1, -2], [-3, -4]], [[9, 10], [11, 12]], [[13, 14], [15, 16]]],
+            'absorbing': [[False, True], [False, False], [False, False]],
+            'last': [[True, True], [False, False], [False, True]]}
+    assert list(got) == list(want)
+    for name, v in want.items():
+        w = torch.tensor(v, dtype=torch.bool if name in ('absorbing', 'last') else f64)
+        assert got[name].dtype == w.dtype and torch.equal(got[name], w), name
+    only_first = lay.unpack(rec, ends, n_ends=1)['next_obs']                  # the second row is past the count: not applied
+    assert torch.equal(only_first[0], torch.tensor([[5.0, 6.0], [-3.0, -4.0]], dtype=f64))
+
+
+def test_packed_output_buffer():
+    """DeviceEnv._packed_out: empty when the env axis is not padded, zero padding rows otherwise (its own or the caller's
+    buffer), and a caller's buffer of the wrong shape, dtype or strides is refused."""
+    import pytest
+    from rl_on_manifold_amd._device_env import DeviceEnv
+    stub, seen = _Stub(B=3), []
+    T, F = 4, 11
+    real_empty, real_zeros = torch.empty, torch.zeros
+    try:
+        torch.empty = lambda *a, **kw: seen.append('empty') or real_empty(*a, **kw)
+        torch.zeros = lambda *a, **kw: seen.append('zeros') or real_zeros(*a, **kw)
+        own = DeviceEnv._packed_out(stub, T, 3, F, None)
+        padded = DeviceEnv._packed_out(stub, T, 5, F, None)
+    finally:
+        torch.empty, torch.zeros = real_empty, real_zeros
+    assert seen == ['empty', 'zeros']                                     # ld == B allocates without zeroing
+    assert own.shape == (T, 3, F) and own.dtype == stub.dtype and own.is_contiguous()
+    assert padded.shape == (T, 5, F) and bool((padded[:, 3:] == 0).all())
+    mine = torch.full((T, 5, F), -777.0, dtype=torch.float64)
+    assert DeviceEnv._packed_out(stub, T, 5, F, mine) is mine
+    assert bool((mine[:, 3:] == 0).all()) and bool((mine[:, :3] == -777.0).all())
+    for bad in (torch.zeros((T, 4, F), dtype=torch.float64), torch.zeros((T, 5, F), dtype=torch.float32),
+                torch.zeros((T, 5, 2 * F), dtype=torch.float64)[..., ::2]):
+        with pytest.raises(ValueError, match='must be a contiguous'):
+            DeviceEnv._packed_out(stub, T, 5, F, bad)
+
+
+def test_the_device_environments_share_one_host_layer():
+    from rl_on_manifold_amd._device_env import DeviceEnv
+    from rl_on_manifold_amd.engine import BatchedAtacomEnv
+    from rl_on_manifold_amd.point import BatchedPointReachEnv
+    for cls in (BatchedAtacomEnv, BatchedPointReachEnv):
+        assert issubclass(cls, DeviceEnv)
+        for name in ('_as_dev', '_check_io', '_stream', '_on_my_device', 'unpack_records', 'close', '__del__'):
+            assert name not in vars(cls) and name in vars(DeviceEnv), (cls.__name__, name)
