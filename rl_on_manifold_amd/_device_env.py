@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .rollout import record_fields, unpack_fields
+from .rollout import compact_record_fields, record_fields, unpack_fields
 
 
 def _ptr(t):
@@ -33,6 +33,8 @@ class DeviceEnv:
     `_h` (the library and its handle)."""
 
     _destroy = None                    # name of the library function that frees `_h`
+    # how a compact collection that overflowed its exception list is retried (the end of rollout_compact's message)
+    _compact_retry = "take a snapshot() before the call to retry it with a larger ends_capacity"
 
     def _init_device(self, device, dtype, check, not_a_gpu):
         """`check`: the library's return-code checker; `not_a_gpu`: the exception to raise for a device that is no GPU."""
@@ -128,6 +130,31 @@ class DeviceEnv:
         net = policy.as_struct(self)
         nz = None if noise is None else self._as_dev(noise, (T, B, k))
         return T, None, C.byref(net), _ptr(nz), (net, nz)
+
+    def _rollout_compact(self, call, T, batch_stride, ends_capacity, out):
+        """The host side of a collection in the compact record format (rollout.CompactRecordLayout): the records and the
+        exception rows allocated or validated, `call(records, ld, ends or None, capacity, n_ends)` -- the subclass's library
+        call -- issued, and the count read back (ONE synchronisation of the current stream).
+        -> (records [T + 1, ld, Fc], ends[:n], n).  Raises ValueError when the count exceeds the capacity."""
+        B = self.batch
+        _, Fc, E = compact_record_fields(self.obs_dim, self.dims['null'])
+        ld = B if batch_stride is None else int(batch_stride)
+        cap = max(T - 1, 0) * B if ends_capacity is None else int(ends_capacity)
+        if cap < 0:
+            raise ValueError("ends_capacity must be >= 0")
+        rec, ends = (None, self._empty(cap, E)) if out is None else out
+        rec = self._packed_out(T + 1, ld, Fc, rec, 'out[0]')
+        if ends.dim() != 2 or ends.shape[0] < cap or ends.shape[1] != E or not ends.is_contiguous() \
+                or ends.dtype != self.dtype or not self._on_my_device(ends):
+            raise ValueError("out[1] must be a contiguous [>= %d, %d] tensor of the engine's dtype on %s"
+                             % (cap, E, self.device))
+        n_ends = self._empty(1, dtype=torch.int32)
+        call(rec, ld, ends if cap > 0 else None, cap, n_ends)
+        n = int(n_ends.item())
+        if n > cap:
+            raise ValueError("rollout_compact: %d episode-end rows, capacity %d -- the rows past the capacity were not written. "
+                             "The engine has advanced: %s" % (n, cap, self._compact_retry))
+        return rec, ends[:n], n
 
     def unpack_records(self, rec):
         """Views into packed records [..., record_dim] (no copy)."""

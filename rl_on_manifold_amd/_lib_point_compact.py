@@ -1,0 +1,34 @@
+"""ctypes binding of libatacom_point_compact.so (include/atacom_point_compact_hip.h): the collision-avoidance task's rollout
+in the compact record format.  It works on the handles of libatacom_point.so (_lib_point) and takes the network description
+of the main library (_lib.AtacomMlp).  No numerics here.
+
+Like _lib.py: if the library is missing or cannot be loaded this module raises -- there is no CPU / PyTorch fallback.
+"""
+import ctypes as C
+import os
+
+from . import _binding
+from ._binding import AtacomError  # noqa: F401
+from ._lib import AtacomMlp
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get('ATACOM_POINT_COMPACT_LIB') or os.path.join(HERE, 'libatacom_point_compact.so')
+
+OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
+
+_vp, _i32, _int, _mlp = C.c_void_p, C.c_int32, C.c_int, C.POINTER(AtacomMlp)
+# {symbol: (restype, argtypes)}: every function of include/atacom_point_compact_hip.h
+SIGNATURES = {
+    'atacom_point_compact_last_error': (C.c_char_p, None),
+    'atacom_point_compact_version': (C.c_char_p, None),
+    'atacom_point_compact_rollout': (_int, [_vp, _i32, _vp, _mlp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
+
+
+def load():
+    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
+    return _binding.load(LIB_PATH, 'libatacom_point_compact.so', SIGNATURES)
+
+
+check = _binding.checker(load, 'atacom_point_compact_last_error')

@@ -3,8 +3,8 @@
     python -m rl_on_manifold_amd.build [--force]
 
 TARGETS below describes each library: libatacom_hip.so (the air-hockey and circle tasks), libatacom_point.so (the
-collision-avoidance task) and libatacom_point_policy.so (its rollout with the actor network in the kernel).  A library is
-one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
+collision-avoidance task), libatacom_point_policy.so (its rollout with the actor network in the kernel) and
+libatacom_point_compact.so (that rollout in the compact record format).  A library is one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
 rl_on_manifold_amd/.  The .so files are git-ignored.
 """
 import os
@@ -59,10 +59,18 @@ TARGETS = {
                            ['atacom_point_policy.hip', 'atacom_point_policy_capi.cpp'],
                            ('atacom_point_policy.h', 'atacom_point_policy_ops.h'), ('point',),
                            ('atacom_hip.h', 'atacom_point_hip.h', 'atacom_point_policy_hip.h'), False),
+    # The task's rollout in the compact record format is a fourth library (include/atacom_point_compact_hip.h): it borrows the
+    # handles of libatacom_point.so and the network, LDS layout and argument checks of libatacom_point_policy.so, and keeps
+    # the kernel census of the other three as it is.
+    'point_compact': Target(_lib_out('ATACOM_POINT_COMPACT_LIB_OUT', 'libatacom_point_compact.so'),
+                            ['atacom_point_compact.hip', 'atacom_point_compact_capi.cpp'],
+                            ('atacom_point_compact.h', 'atacom_point_compact_ops.h'), ('point', 'point_policy'),
+                            ('atacom_hip.h', 'atacom_point_hip.h', 'atacom_point_policy_hip.h', 'atacom_point_compact_hip.h'),
+                            False),
 }
-_MAIN, _POINT, _POINT_POLICY = (TARGETS[k] for k in ('hip', 'point', 'point_policy'))
-LIB, LIB_POINT, LIB_POINT_POLICY = _MAIN.lib, _POINT.lib, _POINT_POLICY.lib
-UNITS_POINT, UNITS_POINT_POLICY = _POINT.units, _POINT_POLICY.units
+_MAIN, _POINT, _POINT_POLICY, _POINT_COMPACT = (TARGETS[k] for k in ('hip', 'point', 'point_policy', 'point_compact'))
+LIB, LIB_POINT, LIB_POINT_POLICY, LIB_POINT_COMPACT = _MAIN.lib, _POINT.lib, _POINT_POLICY.lib, _POINT_COMPACT.lib
+UNITS_POINT, UNITS_POINT_POLICY, UNITS_POINT_COMPACT = _POINT.units, _POINT_POLICY.units, _POINT_COMPACT.units
 
 
 def _sources(target=_MAIN):
@@ -79,6 +87,10 @@ def _sources_point():
 
 def _sources_point_policy():
     return _sources(_POINT_POLICY)
+
+
+def _sources_point_compact():
+    return _sources(_POINT_COMPACT)
 
 
 def _stale(target):
@@ -98,6 +110,10 @@ def needs_build_point():
 
 def needs_build_point_policy():
     return _stale(_POINT_POLICY)
+
+
+def needs_build_point_compact():
+    return _stale(_POINT_COMPACT)
 
 
 # kernel-tuning builds: ATACOM_KEEP_OBJ=1 keeps the objects of a build; ATACOM_ONLY_UNITS=a.hip,b.hip then recompiles only
@@ -174,8 +190,13 @@ def build_point_policy(force=False, verbose=True):
     return _build(_POINT_POLICY, force, verbose)
 
 
+def build_point_compact(force=False, verbose=True):
+    """libatacom_point_compact.so: two units; the eight compact kernels take about a minute."""
+    return _build(_POINT_COMPACT, force, verbose)
+
+
 if __name__ == '__main__':
-    for _b in (build, build_point, build_point_policy):
+    for _b in (build, build_point, build_point_policy, build_point_compact):
         _b(force='--force' in sys.argv)
     for _t in TARGETS.values():
         print(_t.lib)

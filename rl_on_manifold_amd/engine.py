@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._device_env import DeviceEnv, _ptr   # _ptr: also imported from here by tests and tools
-from .rollout import compact_record_fields, record_fields
+from .rollout import record_fields
 from .spaces import Box, MDPInfo
 
 _ENV_IDS = {'circle': _lib.ENV_CIRCLE, 'A': _lib.ENV_CIRCLE, 'planar': _lib.ENV_PLANAR, 'H': _lib.ENV_PLANAR,
@@ -296,28 +296,12 @@ class BatchedAtacomEnv(DeviceEnv):
         (records, ends) caller buffers of those shapes (ends [ends_capacity, D + 2]); padding rows are zeroed as in
         rollout_packed.  Reads the row count back: synchronises the current stream once.  Raises ValueError when the count
         exceeds the capacity -- the rows past it are lost, and the engine has advanced all the same."""
-        B = self.batch
-        _, Fc, E = compact_record_fields(self.obs_dim, self.dims['null'])
         T, a_ptr, net_ref, noise_ptr, _keep = self._source(actions, policy, n_steps, noise)
-        ld = B if batch_stride is None else int(batch_stride)
-        cap = max(T - 1, 0) * B if ends_capacity is None else int(ends_capacity)
-        if cap < 0:
-            raise ValueError("ends_capacity must be >= 0")
-        rec, ends = (None, self._empty(cap, E)) if out is None else out
-        rec = self._packed_out(T + 1, ld, Fc, rec, 'out[0]')
-        if ends.dim() != 2 or ends.shape[0] < cap or ends.shape[1] != E or not ends.is_contiguous() \
-                or ends.dtype != self.dtype or not self._on_my_device(ends):
-            raise ValueError("out[1] must be a contiguous [>= %d, %d] tensor of the engine's dtype on %s"
-                             % (cap, E, self.device))
-        n_ends = self._empty(1, dtype=torch.int32)
-        self._check(self._lib.atacom_rollout_compact(self._h, T, a_ptr, net_ref, noise_ptr, _ptr(rec), ld,
-                                                     _ptr(ends) if cap > 0 else None, cap, _ptr(n_ends), self._stream()))
-        n = int(n_ends.item())
-        if n > cap:
-            raise ValueError("rollout_compact: %d episode-end rows, capacity %d -- the rows past the capacity were not written. "
-                             "The engine has advanced: take a snapshot() before the call to retry it with a larger "
-                             "ends_capacity" % (n, cap))
-        return rec, ends[:n], n
+
+        def call(rec, ld, ends, cap, n_ends):
+            self._check(self._lib.atacom_rollout_compact(self._h, T, a_ptr, net_ref, noise_ptr, _ptr(rec), ld, _ptr(ends), cap,
+                                                         _ptr(n_ends), self._stream()))
+        return self._rollout_compact(call, T, batch_stride, ends_capacity, out)
 
     def _lanes(self):
         a, b = C.c_int32(0), C.c_int32(0)

@@ -5,7 +5,8 @@ atacom/environments/collision_avoidance/collision_avoidance_atacom.py:8) on liba
   PointReachAtacom       batch-1 numpy facade with the reference's constructor, argument for argument
 
 All arithmetic happens in the libraries (hand-written HIP, gfx950); this file only moves pointers.  Collection with an
-MlpPolicy (rollout_policy, rollout_packed) runs the fused kernel of libatacom_point_policy.so on the same handle.
+MlpPolicy (rollout_policy, rollout_packed) runs the fused kernel of libatacom_point_policy.so on the same handle, and
+rollout_compact the kernel of libatacom_point_compact.so.
 
 Random numbers.  The reference draws the obstacles' reset positions and random-walk accelerations from numpy's global
 generator.  Here a call either receives the draws (`draws=`, the values np.random.uniform returned) or, by default,
@@ -17,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib_point, _lib_point_policy
+from . import _lib_point, _lib_point_compact, _lib_point_policy
 from ._device_env import DeviceEnv, _ptr, step_to_host
 from .rollout import record_fields
 from .spaces import Box, MDPInfo
@@ -25,6 +26,7 @@ from .spaces import Box, MDPInfo
 
 class BatchedPointReachEnv(DeviceEnv):
     _destroy = 'atacom_point_destroy'
+    _compact_retry = "keep get_state() from before the call (set_state() puts it back) to retry it with a larger ends_capacity"
 
     def __init__(self, batch, n_objects=4, random_walk=True, time_step=0.01, horizon=1000, gamma=0.99, seed=0,
                  auto_reset=True, device='cuda:0', dtype=torch.float32):
@@ -169,6 +171,28 @@ class BatchedPointReachEnv(DeviceEnv):
         _lib_point_policy.check(self._policy_lib().atacom_point_policy_rollout_packed(
             self._h, T, a_ptr, net_ref, noise_ptr, _ptr(d), _ptr(out), ld, self._stream()))
         return out
+
+    def rollout_compact(self, actions=None, policy=None, n_steps=None, noise=None, draws=None, out=None, batch_stride=None,
+                        ends_capacity=None):
+        """rollout_packed() in the compact record format (atacom_point_compact_rollout), which does not repeat next_obs -- the
+        surface of BatchedAtacomEnv.rollout_compact plus `draws`.  Returns (records [T + 1, batch_stride, D + 5], ends [n, D + 2], n):
+          records rows 0..T-1 = [obs | action | reward | absorbing | last], row T = [obs after the last step | zeros];
+          ends = one row [t, b, terminal obs] per episode end at t < T-1 of an auto-resetting engine, in no particular order.
+        rollout.CompactRecordLayout rebuilds the full records' fields from them.  ends_capacity (default (T-1) * batch, the
+        worst case) rows are allocated on the device; at the task's horizon of 1000 about batch * T / 1000 are used.  `out` = (records,
+        ends) caller buffers of those shapes (ends [ends_capacity, D + 2]); padding rows are zeroed as in rollout_packed.
+        Reads the row count back: synchronises the current stream once.  Raises ValueError when the count exceeds the
+        capacity -- the rows past it are lost, and the engine has advanced all the same."""
+        if actions is None and policy is not None and not hasattr(policy, 'as_struct'):
+            raise ValueError("rollout_compact takes an MlpPolicy (as_struct); a plain callable goes through rollout_policy")
+        T, a_ptr, net_ref, noise_ptr, _keep = self._source(actions, policy, n_steps, noise)
+        d = None if draws is None else self._as_dev(draws, (T, self.batch, self.n_objects, 2))
+        lib = _lib_point_compact.load()
+
+        def call(rec, ld, ends, cap, n_ends):
+            _lib_point_compact.check(lib.atacom_point_compact_rollout(
+                self._h, T, a_ptr, net_ref, noise_ptr, _ptr(d), _ptr(rec), ld, _ptr(ends), cap, _ptr(n_ends), self._stream()))
+        return self._rollout_compact(call, T, batch_stride, ends_capacity, out)
 
     def get_constraints_logs(self, clear=True):
         """(c_avg, c_max, c_dq_max) over every step of every environment since the last clear; c_dq_max is the
