@@ -11,6 +11,7 @@ __global__ void __launch_bounds__(64) k(float* out, long long* cyc, int iters) {
     float b = 1.0001f, c = 0.5f;
     typedef float f2 __attribute__((ext_vector_type(2)));
     f2 p0 = {a0, a1}, p1 = {a2, a3}, p2 = {a4, a5}, p3 = {a6, a7}, pb = {b, b}, pc = {c, c};
+    f2 d0 = p0, d1 = p1, d2 = p2, d3 = p3;
     long long t0 = __builtin_readcyclecounter();
     for (int it = 0; it < iters; ++it) {
         if (MODE == 0) {  // dependent v_fma_f32 chain
@@ -53,10 +54,24 @@ __global__ void __launch_bounds__(64) k(float* out, long long* cyc, int iters) {
             asm volatile(REP8(REP8("v_accvgpr_write_b32 a0, %0\n\tv_accvgpr_read_b32 %0, a0\n\t")) : "+v"(a0) :: "a0");
         } else if (MODE == 19) {  // v_cmp + cndmask e64 dependent
             asm volatile(REP8(REP8("v_cmp_gt_f32_e64 s[20:21], %0, %1\n\tv_cndmask_b32_e64 %0, %0, %1, s[20:21]\n\t")) : "+v"(a0) : "v"(b) : "s20", "s21");
+        } else if (MODE == 20) {  // v_mov_b32_dpp quad_perm, 4 independent (fixed source)
+            asm volatile(REP8(REP8("v_mov_b32_dpp %0, %4 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %1, %4 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %2, %4 quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %3, %4 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t")) : "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b));
+        } else if (MODE == 21) {  // v_mov_b64_dpp row_newbcast, 4 independent (fixed source pair)
+            asm volatile(REP8(REP8("v_mov_b64_dpp %0, %4 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %2, %4 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\tv_mov_b64_dpp %3, %4 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t")) : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3) : "v"(pb));
+        } else if (MODE == 22) {  // 8-lane broadcast of a pair, two 64-bit moves onto one destination: banks 0x3, then 0xC; 4 destinations
+            asm volatile(REP8(REP8("v_mov_b64_dpp %0, %4 row_newbcast:1 row_mask:0xf bank_mask:0x3\n\tv_mov_b64_dpp %0, %4 row_newbcast:9 row_mask:0xf bank_mask:0xc\n\tv_mov_b64_dpp %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0x3\n\tv_mov_b64_dpp %1, %4 row_newbcast:10 row_mask:0xf bank_mask:0xc\n\tv_mov_b64_dpp %2, %4 row_newbcast:3 row_mask:0xf bank_mask:0x3\n\tv_mov_b64_dpp %2, %4 row_newbcast:11 row_mask:0xf bank_mask:0xc\n\tv_mov_b64_dpp %3, %4 row_newbcast:4 row_mask:0xf bank_mask:0x3\n\tv_mov_b64_dpp %3, %4 row_newbcast:12 row_mask:0xf bank_mask:0xc\n\t")) : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3) : "v"(pb));
+        } else if (MODE == 23) {  // the same broadcast as four 32-bit moves: quad_perm per half, then row_half_mirror into the other quad's banks;
+                                  // two pairs interleaved, so that every mirror reads a register written four instructions earlier (no wait states due)
+            asm volatile(REP8(REP8("v_mov_b32_dpp %0, %4 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %1, %5 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %2, %4 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %3, %5 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mov_b32_dpp %0, %0 row_half_mirror row_mask:0xf bank_mask:0xa\n\tv_mov_b32_dpp %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa\n\tv_mov_b32_dpp %2, %2 row_half_mirror row_mask:0xf bank_mask:0xa\n\tv_mov_b32_dpp %3, %3 row_half_mirror row_mask:0xf bank_mask:0xa\n\t")) : "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b), "v"(c));
+        } else if (MODE == 24) {  // 64-bit broadcast, then a v_pk_mul_f32 that consumes it (the broadcast's source is fixed: no DPP read hazard)
+            asm volatile(REP8(REP8("v_mov_b64_dpp %0, %2 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\tv_pk_mul_f32 %1, %1, %0\n\t")) : "+v"(d0), "+v"(p0) : "v"(pb));
+        } else if (MODE == 25) {  // for comparison: a 32-bit broadcast, then a v_mul_f32 that consumes it
+            asm volatile(REP8(REP8("v_mov_b32_dpp %0, %2 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\tv_mul_f32 %1, %1, %0\n\t")) : "+v"(a4), "+v"(a0) : "v"(b));
         }
     }
     long long t1 = __builtin_readcyclecounter();
-    out[blockIdx.x * 64 + threadIdx.x] = a0 + a1 + a2 + a3 + p0.x + p0.y + p1.x + p2.x + p3.y;
+    out[blockIdx.x * 64 + threadIdx.x] = a0 + a1 + a2 + a3 + p0.x + p0.y + p1.x + p2.x + p3.y
+        + a4 + a5 + a6 + a7 + d0.x + d0.y + d1.x + d1.y + d2.x + d2.y + d3.x + d3.y;
     if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
 }
 template <int MODE> void run(const char* name, int ninstr_per_iter, int waves_per_block = 1) {
@@ -96,5 +111,12 @@ int main() {
     run<14>("s_and_b64 dependent", 64);
     run<15>("s_and_b64 + v_fma alternating (2)", 128);
     run<18>("accvgpr write+read (2)", 128);
+    // 8-lane broadcasts of a row pair (profiles/pair_broadcast.md)
+    run<20>("v_mov_b32_dpp quad_perm, 4 independent", 256);
+    run<21>("v_mov_b64_dpp row_newbcast, 4 independent", 256);
+    run<22>("pair bcast: 2 x v_mov_b64_dpp (per move)", 512);
+    run<23>("pair bcast: 4 x v_mov_b32_dpp (per move)", 512);
+    run<24>("v_mov_b64_dpp + dependent v_pk_mul_f32 (2)", 128);
+    run<25>("v_mov_b32_dpp + dependent v_mul_f32 (2)", 128);
     return 0;
 }

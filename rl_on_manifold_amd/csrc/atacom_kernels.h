@@ -905,10 +905,21 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
             rref_apply_quad<T, NN, ND, LG>(nb0, nb, alphaq, P.rref_tol, nmu0, nmu, lq);
             ATACOM_MARK("MU_gather");
             mu[0] = nmu0 - x0;
+            if constexpr (PAIR_BCAST64<T, LG> && S == 2) {
+                // the lane's two slots travel as one pair: lane l delivers mu[l + 1] and mu[l + 9]
+                const vec2<T> d = vec2<T>{nmu[0], nmu[1]} - vec2<T>{x[0], x[1]};
+                static_for<0, LG>([&](auto lc) {
+                    constexpr int l = decltype(lc)::value;
+                    const vec2<T> g = qbcast2<l, LG>(d);
+                    if constexpr (l + 1 < NN) mu[l + 1] = g.x;
+                    if constexpr (l + 1 + LG < NN) mu[l + 1 + LG] = g.y;
+                });
+            } else {
             static_for<1, NN>([&](auto nc) {                        // gather mu back to every lane of the group
                 constexpr int n = decltype(nc)::value;
                 mu[n] = qbcast<(n - 1) % LG, LG>(nmu[(n - 1) / LG] - x[(n - 1) / LG]);
             });
+            }
         }
         ATACOM_MARK("SUB_integrate");
 #pragma unroll

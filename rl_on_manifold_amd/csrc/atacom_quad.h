@@ -14,8 +14,9 @@
 //   * vectors over the M rows (rhs y, the bidiagonal d / e, left reflectors u) are REPLICATED in the four
 //     lanes and computed redundantly -- their values stay bitwise identical across the quad because every
 //     cross-lane sum uses the same commutative butterfly;
-//   * cross-lane traffic is DPP only (quad_perm; row_half_mirror for 8 lanes): a broadcast is one v_mov_dpp, a quad
-//     sum two v_add_f32_dpp; no LDS, no ds_bpermute, no barriers;
+//   * cross-lane traffic is DPP only (quad_perm; row_half_mirror for 8 lanes; row_newbcast on 64-bit moves for the row
+//     pairs of the float32 8-lane kernels, see qbcast2): a broadcast is one v_mov_dpp, a quad sum two v_add_f32_dpp; no
+//     LDS, no ds_bpermute, no barriers;
 //   * "my column of a replicated array" is picked by a one-hot FMA blend, never by a select chain on lq (the
 //     optimiser turns those into a divergent 4-way switch).
 // The arithmetic is the same Householder bidiagonalisation / rref chart as atacom_linalg.h (the one-lane-per-env
@@ -256,8 +257,29 @@ __device__ __forceinline__ void split_sum(double (&h)[H2]) {
     }
 }
 
+// ---- broadcast of a two-wide vector.  float, 8 lanes (PAIR_BCAST64): a row pair lives in an aligned register pair, and the
+// 64-bit DPP move takes row_newbcast (every lane of a 16-lane row reads lane n of that row): two INDEPENDENT moves, one
+// written to the banks of the row's lower group (lane O) and one to the upper group's (lane 8 + O), instead of the four
+// 32-bit moves of qbcast, of which the second pair waits for the first.  Each group reads a lane of its own, so a group
+// whose lanes are switched off (an odd batch's last row) neither feeds nor disturbs its neighbour.  Two details keep the
+// form at two instructions (seen in the ISA, profiles/pair_broadcast.md):
+//   * the first move's `old` operand is NOT the source -- the source is still live, so the allocator would copy it first;
+//   * it is an undefined value of its own per call site: the volatile on the empty asm keeps CSE from merging the sites into
+//     one definition, which would then be copied in front of every broadcast.  The asm emits nothing.
+// Data movement only: the bits are those of qbcast.  Every other mapping and double keep qbcast's moves.
+template <typename T, int LN> constexpr bool PAIR_BCAST64 = (LN == 8) && std::is_same<T, float>::value;
 template <int O, int LN = 4, typename T> __device__ __forceinline__ vec2<T> qbcast2(vec2<T> v) {
-    return vec2<T>{qbcast<O, LN>(v.x), qbcast<O, LN>(v.y)};
+    if constexpr (PAIR_BCAST64<T, LN>) {
+        constexpr int DPP_ROW_NEWBCAST = 0x150;                  // + lane of the row
+        const long long b = __builtin_bit_cast(long long, v);
+        long long u;
+        asm volatile("" : "=v"(u));
+        long long t = __builtin_amdgcn_update_dpp(u, b, DPP_ROW_NEWBCAST + O, 0xF, 0x3, false);
+        t = __builtin_amdgcn_update_dpp(t, b, DPP_ROW_NEWBCAST + 8 + O, 0xF, 0xC, false);
+        return __builtin_bit_cast(vec2<T>, t);
+    } else {
+        return vec2<T>{qbcast<O, LN>(v.x), qbcast<O, LN>(v.y)};
+    }
 }
 // value held by lane L (compile time) of the group
 template <int L, int LN = 4, typename V> __device__ __forceinline__ V qfrom(V v) { return qbcast<L, LN>(v); }
@@ -393,9 +415,17 @@ __device__ __forceinline__ void bidiag_solve_null_quad_inl(AF&& aget, A0F&& a0ge
                 if constexpr (first) e[i] = (hi == 0) ? c0[p0].y : c0[p0].x;
                 else e[i] = qfrom<li, LN>(hi == 0 ? a2[si][p0].y : a2[si][p0].x);
             } else {
+            // float, 8 lanes: the pivot column's row pairs are broadcast FIRST (qbcast2, two moves a pair) and every lane forms
+            // the sum of squares, the pivot element and u from lane li's values -- the same operations on the same values in
+            // the same order as in lane li, so the broadcasts of the sum and of the pivot element (four moves) disappear
+            constexpr bool bfirst = !first && PAIR_BCAST64<T, LN>;
             V2 colp[MP];
-#pragma unroll
-            for (int p = p0; p < MP; ++p) colp[p] = first ? c0[p] : a2[si][p];
+            static_for<p0, MP>([&](auto pc) {
+                constexpr int p = decltype(pc)::value;
+                if constexpr (first) colp[p] = c0[p];
+                else if constexpr (bfirst) colp[p] = qbcast2<li, LN>(a2[si][p]);
+                else colp[p] = a2[si][p];
+            });
             V2 sq = splat2(T(0));
 #pragma unroll
             for (int p = p0 + 1; p < MP; ++p) sq = fma2(colp[p], colp[p], sq);
@@ -403,6 +433,7 @@ __device__ __forceinline__ void bidiag_solve_null_quad_inl(AF&& aget, A0F&& a0ge
             if constexpr (hi == 1) sup = num<T>::fma(colp[p0].y, colp[p0].y, sup);   // row i+2 shares i+1's pair
             T su, alq;
             if constexpr (first) { su = sup; alq = colp[p0].y; }
+            else if constexpr (bfirst) { su = sup; alq = (hi == 0) ? colp[p0].y : colp[p0].x; }
             else { su = qfrom<li, LN>(sup); alq = qfrom<li, LN>(hi == 0 ? colp[p0].y : colp[p0].x); }
             T betaq, tq;
             const T scq = larfg_scale(alq, su, betaq, tq);
@@ -410,7 +441,7 @@ __device__ __forceinline__ void bidiag_solve_null_quad_inl(AF&& aget, A0F&& a0ge
             V2 u2[MP];
 #pragma unroll
             for (int p = p0; p < MP; ++p) {
-                if constexpr (first) u2[p] = colp[p] * splat2(scq);
+                if constexpr (first || bfirst) u2[p] = colp[p] * splat2(scq);
                 else u2[p] = qbcast2<li, LN>(colp[p]) * splat2(scq);
             }
             if constexpr (hi == 0) u2[p0] = V2{T(0), T(1)};
