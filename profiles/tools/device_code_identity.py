@@ -1,6 +1,6 @@
 """Is the device code of two builds of the package's libraries the same, function by function?  No GPU needed.
 
-    python profiles/tools/device_code_identity.py DIR_A DIR_B      (each holding the three lib*.so of a build)
+    python profiles/tools/device_code_identity.py DIR_A DIR_B [LIB ...]     (each holding the lib*.so of a build; default: LIBS)
 
 For every library, every gfx950 code object inside .hip_fatbin is extracted (as tests/test_kernel_resources.py does) and
 each FUNC symbol's slice of its .text is hashed.  Compared per mangled symbol: the same set of symbols, and identical
@@ -45,11 +45,11 @@ def functions(so):
     return n_kernels, {k: sorted(v) for k, v in out.items()}
 
 
-def main(dir_a, dir_b):
+def main(dir_a, dir_b, libs=LIBS):
     print('| library | kernels A / B | function symbols A / B | in one build only | compared | differing |')
     print('|---|---|---|---|---|---|')
     bad, detail = 0, []
-    for lib in LIBS:
+    for lib in libs:
         (ka, A), (kb, B) = functions(os.path.join(dir_a, lib)), functions(os.path.join(dir_b, lib))
         only = sorted(set(A) ^ set(B))
         differing = sorted(k for k in set(A) & set(B) if A[k] != B[k])
@@ -62,4 +62,4 @@ def main(dir_a, dir_b):
 
 
 if __name__ == '__main__':
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], tuple(sys.argv[3:]) or LIBS))

@@ -15,7 +15,7 @@ def __getattr__(name):
         from . import engine
         return getattr(engine, name)
     if name in ('CircleEnvAtacom', 'AirHockeyPlanarAtacom', 'AirHockeyIiwaAtacom', 'CircleEnvErrorCorrection',
-                'CircleEnvTerminated', 'VectorizedAtacomEnv'):
+                'CircleEnvTerminated', 'VectorizedAtacomEnv', 'VectorizedPointReachEnv'):
         from . import envs
         return getattr(envs, name)
     if name in ('RolloutCollector', 'RecordLayout', 'CompactRecordLayout'):

@@ -28,6 +28,23 @@ def step_to_host(engine, action, **kw):
     return host[:-2].copy(), float(host[-2]), bool(host[-1] != 0.0)
 
 
+def device_mask(env_mask, device, n):
+    """What the vectorised surfaces (envs.VectorizedAtacomEnv, envs.VectorizedPointReachEnv) make of an `env_mask`: uint8 [n] on
+    `device`, or None for "all" -- decided from the argument alone (None), never by looking at the mask's values (that would be
+    a device -> host synchronisation per step).  bool is reinterpreted, uint8 taken as it is, anything else compared with 0."""
+    if env_mask is None:
+        return None
+    m = env_mask if isinstance(env_mask, torch.Tensor) else torch.as_tensor(env_mask)
+    m = m.to(device=device)
+    if m.dtype == torch.bool:
+        m = m.contiguous().view(torch.uint8)
+    elif m.dtype != torch.uint8:
+        m = (m != 0).view(torch.uint8)
+    if tuple(m.shape) != (n,):
+        raise ValueError("env_mask must have shape (%d,), got %s" % (n, tuple(m.shape)))
+    return m.contiguous()
+
+
 class DeviceEnv:
     """Base of the batched environments.  A subclass calls `_init_device`, then sets `batch`, `obs_dim`, `dims`, `_lib` and
     `_h` (the library and its handle)."""
@@ -91,6 +108,13 @@ class DeviceEnv:
         if len(self._io_ok) > 4096:
             self._io_ok.clear()
         self._io_ok.add(key)
+
+    def _nobody(self):
+        """A reset mask that selects nobody: a masked reset with it is "observe the current state" (kept: a captured graph
+        reads it at every replay)."""
+        if getattr(self, '_nobody_mask', None) is None:
+            self._nobody_mask = torch.zeros((self.batch,), device=self.device, dtype=torch.uint8)
+        return self._nobody_mask
 
     def _rollout_buffers(self, T, want_next_obs=True, with_action=True):
         """The time-major output tensors of a T-step collection (flags as uint8)."""

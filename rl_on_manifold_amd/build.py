@@ -3,8 +3,9 @@
     python -m rl_on_manifold_amd.build [--force]
 
 TARGETS below describes each library: libatacom_hip.so (the air-hockey and circle tasks), libatacom_point.so (the
-collision-avoidance task), libatacom_point_policy.so (its rollout with the actor network in the kernel) and
-libatacom_point_compact.so (that rollout in the compact record format).  A library is one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
+collision-avoidance task), libatacom_point_policy.so (its rollout with the actor network in the kernel),
+libatacom_point_compact.so (that rollout in the compact record format) and libatacom_point_vec.so (the task's masked step and
+checkpoint).  A library is one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
 rl_on_manifold_amd/.  The .so files are git-ignored.
 """
 import os
@@ -67,9 +68,17 @@ TARGETS = {
                             ('atacom_point_compact.h', 'atacom_point_compact_ops.h'), ('point', 'point_policy'),
                             ('atacom_hip.h', 'atacom_point_hip.h', 'atacom_point_policy_hip.h', 'atacom_point_compact_hip.h'),
                             False),
+    # The task's masked step and checkpoint are a fifth library (include/atacom_point_vec_hip.h): it borrows the handles and the
+    # environment (atacom_point.h) of libatacom_point.so and keeps the kernel census of the other four as it is.
+    'point_vec': Target(_lib_out('ATACOM_POINT_VEC_LIB_OUT', 'libatacom_point_vec.so'),
+                        ['atacom_point_vec.hip', 'atacom_point_vec_capi.cpp'],
+                        ('atacom_point_vec.h', 'atacom_point_vec_ops.h'), ('point',),
+                        ('atacom_point_hip.h', 'atacom_point_vec_hip.h'), False),
 }
-_MAIN, _POINT, _POINT_POLICY, _POINT_COMPACT = (TARGETS[k] for k in ('hip', 'point', 'point_policy', 'point_compact'))
+_MAIN, _POINT, _POINT_POLICY, _POINT_COMPACT, _POINT_VEC = (TARGETS[k] for k in ('hip', 'point', 'point_policy', 'point_compact',
+                                                                                 'point_vec'))
 LIB, LIB_POINT, LIB_POINT_POLICY, LIB_POINT_COMPACT = _MAIN.lib, _POINT.lib, _POINT_POLICY.lib, _POINT_COMPACT.lib
+LIB_POINT_VEC, UNITS_POINT_VEC = _POINT_VEC.lib, _POINT_VEC.units
 UNITS_POINT, UNITS_POINT_POLICY, UNITS_POINT_COMPACT = _POINT.units, _POINT_POLICY.units, _POINT_COMPACT.units
 
 
@@ -93,6 +102,10 @@ def _sources_point_compact():
     return _sources(_POINT_COMPACT)
 
 
+def _sources_point_vec():
+    return _sources(_POINT_VEC)
+
+
 def _stale(target):
     if not os.path.exists(target.lib):
         return True
@@ -114,6 +127,10 @@ def needs_build_point_policy():
 
 def needs_build_point_compact():
     return _stale(_POINT_COMPACT)
+
+
+def needs_build_point_vec():
+    return _stale(_POINT_VEC)
 
 
 # kernel-tuning builds: ATACOM_KEEP_OBJ=1 keeps the objects of a build; ATACOM_ONLY_UNITS=a.hip,b.hip then recompiles only
@@ -195,8 +212,13 @@ def build_point_compact(force=False, verbose=True):
     return _build(_POINT_COMPACT, force, verbose)
 
 
+def build_point_vec(force=False, verbose=True):
+    """libatacom_point_vec.so: two units, a few seconds."""
+    return _build(_POINT_VEC, force, verbose)
+
+
 if __name__ == '__main__':
-    for _b in (build, build_point, build_point_policy, build_point_compact):
+    for _b in (build, build_point, build_point_policy, build_point_compact, build_point_vec):
         _b(force='--force' in sys.argv)
     for _t in TARGETS.values():
         print(_t.lib)

@@ -218,6 +218,12 @@ class BatchedAtacomEnv(DeviceEnv):
         self._check_step_io(actions, obs, reward, absorbing, last, mask)
         self._launch_step(actions, obs, reward, absorbing, last, mask)
 
+    def observe_into(self, obs):
+        """The observation of the CURRENT state into obs [B, obs_dim]: the masked reset with a mask that selects nobody.
+        Enqueue-only (what GraphedRollout captures)."""
+        self._check_io(obs, (self.batch, self.obs_dim), self.dtype, 'obs')
+        _lib.check(self._lib.atacom_reset(self._h, _ptr(self._nobody()), None, _ptr(obs), self._stream()))
+
     def bind_step(self, actions, obs, reward, absorbing, last=None, mask=None):
         """step_into() with its arguments validated ONCE: returns a zero-argument callable that launches atacom_step (or
         atacom_step_masked) on the caller's current stream with these tensors -- for loops that reuse their buffers and are
@@ -406,6 +412,7 @@ class GraphedRollout:
     copy + step = three kernels per step) 6.2 us per step for the circle against ~20 us for three eager launches.
 
       loop = GraphedRollout(env, policy, n_steps=120)      # policy: obs [B, D] -> actions [B, k], torch ops on env.device
+                                                            # env: a BatchedAtacomEnv or a BatchedPointReachEnv
       data = loop.replay()                                  # dict of static tensors: obs, action, reward, next_obs, absorbing, last
 
     The returned tensors are the graph's static buffers (overwritten by the next replay).  `policy` must be capturable:
@@ -415,7 +422,7 @@ class GraphedRollout:
         self.env, self.T = env, int(n_steps)
         T, dev = self.T, env.device
         self.out = env._rollout_buffers(T)
-        self._none = torch.zeros((env.batch,), device=dev, dtype=torch.uint8)   # reset mask selecting nobody = "observe"
+        env._nobody()                      # the "observe" mask is allocated out here, not inside the capture
         saved = env.snapshot()             # everything: state, statistics, episode counters, servo joints
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -433,10 +440,9 @@ class GraphedRollout:
         env, o = self.env, self.out
         for t in range(n):
             # observation of the CURRENT state (after an auto-reset it differs from the previous step's terminal obs)
-            _lib.check(env._lib.atacom_reset(env._h, _ptr(self._none), None, _ptr(o['obs'][t]), env._stream()))
+            env.observe_into(o['obs'][t])
             o['action'][t].copy_(policy(o['obs'][t]))
-            _lib.check(env._lib.atacom_step(env._h, _ptr(o['action'][t]), _ptr(o['next_obs'][t]), _ptr(o['reward'][t]),
-                                            _ptr(o['absorbing'][t]), _ptr(o['last'][t]), env._stream()))
+            env.step_into(o['action'][t], o['next_obs'][t], o['reward'][t], o['absorbing'][t], o['last'][t])
 
     def replay(self):
         self.graph.replay()

@@ -11,8 +11,9 @@ They are thin: one BatchedAtacomEnv with batch = 1 (or `n_envs` > 1 for a vector
 import numpy as np
 import torch
 
-from ._device_env import step_to_host
+from ._device_env import device_mask, step_to_host
 from .engine import BatchedAtacomEnv
+from .point import BatchedPointReachEnv
 
 DEFEND_START_RANGE = np.array([[0.25, 0.65], [-0.4, 0.4]])   # mushroom_rl AirHockeyDefend.start_range [upstream]
 HIT_RANGE = np.array([[-0.6, -0.2], [-0.4, 0.4]])      # env_hitting.py:11
@@ -207,19 +208,7 @@ class VectorizedAtacomEnv:
         self._engine.stop()
 
     def _mask(self, env_mask):
-        """uint8 [n_envs] on the device, or None for "all" -- decided from the argument alone (None), never by looking at
-        the mask's values (that would be a device -> host synchronisation per step)."""
-        if env_mask is None:
-            return None
-        m = env_mask if isinstance(env_mask, torch.Tensor) else torch.as_tensor(env_mask)
-        m = m.to(device=self._engine.device)
-        if m.dtype == torch.bool:
-            m = m.contiguous().view(torch.uint8)
-        elif m.dtype != torch.uint8:
-            m = (m != 0).view(torch.uint8)
-        if tuple(m.shape) != (self.number,):
-            raise ValueError("env_mask must have shape (%d,), got %s" % (self.number, tuple(m.shape)))
-        return m.contiguous()
+        return device_mask(env_mask, self._engine.device, self.number)
 
     def reset_all(self, env_mask=None, state=None):
         """Reset the masked environments (all if None); returns (observations [n_envs, D], {})."""
@@ -229,6 +218,64 @@ class VectorizedAtacomEnv:
     def step_all(self, env_mask, action):
         """One env step of the masked environments.  action [n_envs, k] (rows of masked-out environments are ignored)."""
         obs, r, ab, info = self._engine.step(action, mask=self._mask(env_mask))
+        self._obs = obs
+        return obs, r, ab, info
+
+    def get_constraints_logs(self):
+        return self._engine.get_constraints_logs()
+
+
+class VectorizedPointReachEnv:
+    """`n_envs` collision-avoidance environments (PointReachAtacom) behind the surface of VectorizedAtacomEnv, for a vectorised
+    Core: `reset_all(env_mask)`, `step_all(env_mask, action)`, `number`, `info`; torch tensors on the device in and out.
+
+      env = VectorizedPointReachEnv(8192, n_objects=4, random_walk=True)
+      obs, _ = env.reset_all()
+      obs, reward, absorbing, info = env.step_all(mask, actions)         # info['last'] marks finished episodes
+
+    Environments whose mask entry is False sit the call out ON THE DEVICE (`atacom_point_vec_step_masked`): state, counters and
+    constraint statistics untouched, their current observation, reward 0 and False flags reported, and no random numbers
+    consumed -- the generator is keyed by each environment's own episode and step counters.  A `step_all` is one kernel launch
+    whatever the mask, and is capturable in a HIP graph.  `**kwargs` are BatchedPointReachEnv's (n_objects, random_walk,
+    time_step, horizon, gamma, seed, auto_reset, device, dtype).  Like the reference's constructor this one does not reset:
+    the circle centres of random_walk=False are those of the FIRST `reset_all`, whose `draws` the caller may supply."""
+
+    def __init__(self, n_envs, **kwargs):
+        self._engine = BatchedPointReachEnv(n_envs, **kwargs)
+        self.number = int(n_envs)
+        self.dims = self._engine.dims
+        self._obs = None
+
+    @property
+    def info(self):
+        return self._engine.info
+
+    @property
+    def engine(self):
+        return self._engine
+
+    def seed(self, seed):
+        self._engine.seed(seed)
+
+    def render_all(self, env_mask=None, record=False):
+        pass
+
+    def stop(self):
+        self._engine.stop()
+
+    def _mask(self, env_mask):
+        return device_mask(env_mask, self._engine.device, self.number)
+
+    def reset_all(self, env_mask=None, draws=None):
+        """Reset the masked environments (all if None); draws (optional) [n_envs, n_objects, 2], values of U(2, 8).  Returns
+        (observations [n_envs, D], {})."""
+        self._obs = self._engine.reset(mask=self._mask(env_mask), draws=draws)
+        return self._obs, {}
+
+    def step_all(self, env_mask, action, draws=None):
+        """One env step of the masked environments.  action [n_envs, 2] and draws (optional) [n_envs, n_objects, 2], values
+        of U(-1, 1): rows of masked-out environments are ignored."""
+        obs, r, ab, info = self._engine.step(action, draws=draws, mask=self._mask(env_mask))
         self._obs = obs
         return obs, r, ab, info
 

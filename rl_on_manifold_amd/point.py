@@ -5,8 +5,9 @@ atacom/environments/collision_avoidance/collision_avoidance_atacom.py:8) on liba
   PointReachAtacom       batch-1 numpy facade with the reference's constructor, argument for argument
 
 All arithmetic happens in the libraries (hand-written HIP, gfx950); this file only moves pointers.  Collection with an
-MlpPolicy (rollout_policy, rollout_packed) runs the fused kernel of libatacom_point_policy.so on the same handle, and
-rollout_compact the kernel of libatacom_point_compact.so.
+MlpPolicy (rollout_policy, rollout_packed) runs the fused kernel of libatacom_point_policy.so on the same handle,
+rollout_compact the kernel of libatacom_point_compact.so, and the masked step and the checkpoint (step(mask=...), snapshot,
+restore) those of libatacom_point_vec.so.
 
 Random numbers.  The reference draws the obstacles' reset positions and random-walk accelerations from numpy's global
 generator.  Here a call either receives the draws (`draws=`, the values np.random.uniform returned) or, by default,
@@ -18,7 +19,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib_point, _lib_point_compact, _lib_point_policy
+from . import _lib_point, _lib_point_compact, _lib_point_policy, _lib_point_vec
 from ._device_env import DeviceEnv, _ptr, step_to_host
 from .rollout import record_fields
 from .spaces import Box, MDPInfo
@@ -26,7 +27,6 @@ from .spaces import Box, MDPInfo
 
 class BatchedPointReachEnv(DeviceEnv):
     _destroy = 'atacom_point_destroy'
-    _compact_retry = "keep get_state() from before the call (set_state() puts it back) to retry it with a larger ends_capacity"
 
     def __init__(self, batch, n_objects=4, random_walk=True, time_step=0.01, horizon=1000, gamma=0.99, seed=0,
                  auto_reset=True, device='cuda:0', dtype=torch.float32):
@@ -70,20 +70,43 @@ class BatchedPointReachEnv(DeviceEnv):
         _lib_point.check(self._lib.atacom_point_reset(self._h, _ptr(m), _ptr(d), _ptr(obs), self._stream()))
         return obs
 
-    def step(self, actions, draws=None):
-        """actions [B, 2]; draws (optional) [B, n_objects, 2], values of U(-1, 1) for the random walk.
+    def _vec_lib(self):
+        if getattr(self, '_vlib', None) is None:
+            self._vlib = _lib_point_vec.load()
+        return self._vlib
+
+    def _launch_step(self, actions, draws, obs, reward, absorbing, last, mask):
+        """atacom_point_step, or atacom_point_vec_step_masked when there is a mask, on the caller's current stream."""
+        if mask is None:
+            _lib_point.check(self._lib.atacom_point_step(self._h, _ptr(actions), _ptr(draws), _ptr(obs), _ptr(reward),
+                                                         _ptr(absorbing), _ptr(last), self._stream()))
+        else:
+            _lib_point_vec.check(self._vec_lib().atacom_point_vec_step_masked(
+                self._h, _ptr(mask), _ptr(actions), _ptr(draws), _ptr(obs), _ptr(reward), _ptr(absorbing), _ptr(last),
+                self._stream()))
+
+    def step(self, actions, draws=None, mask=None):
+        """actions [B, 2]; draws (optional) [B, n_objects, 2], values of U(-1, 1) for the random walk; mask (optional, [B] bool
+        / uint8): environments with a zero entry sit the call out ON THE DEVICE -- state, counters and statistics untouched, no
+        random numbers consumed, obs = their current observation, reward 0, flags False; their action and draw rows are not read.
         -> (obs, reward, absorbing, {'last': ...}) in fresh tensors."""
         B = self.batch
         a = self._as_dev(actions, (B, 2))
         d = None if draws is None else self._as_dev(draws, (B, self.n_objects, 2))
         obs, reward = self._empty(B, self.obs_dim), self._empty(B)
         absorbing, last = self._empty(B, dtype=torch.uint8), self._empty(B, dtype=torch.uint8)
-        _lib_point.check(self._lib.atacom_point_step(self._h, _ptr(a), _ptr(d), _ptr(obs), _ptr(reward), _ptr(absorbing),
-                                                     _ptr(last), self._stream()))
+        if mask is not None:
+            mask = mask.view(torch.uint8) if (isinstance(mask, torch.Tensor) and mask.dtype == torch.bool
+                                              and self._on_my_device(mask) and mask.is_contiguous()) \
+                else self._as_dev(mask, (B,), torch.uint8)
+            if tuple(mask.shape) != (B,):
+                raise ValueError("expected a mask of shape (%d,), got %s" % (B, tuple(mask.shape)))
+        self._launch_step(a, d, obs, reward, absorbing, last, mask)
         return obs, reward, absorbing.view(torch.bool), {'last': last.view(torch.bool)}
 
-    def step_into(self, actions, obs, reward, absorbing, last=None, draws=None):
-        """Allocation-free variant of step(): caller-owned output tensors (uint8 for the flags)."""
+    def step_into(self, actions, obs, reward, absorbing, last=None, draws=None, mask=None):
+        """Allocation-free variant of step(): caller-owned output tensors (uint8 for the flags).  `mask` (uint8 [B], optional):
+        environments with a zero byte sit the call out on the device (atacom_point_vec_step_masked)."""
         B = self.batch
         self._check_io(actions, (B, 2), self.dtype, 'actions')
         self._check_io(draws, (B, self.n_objects, 2), self.dtype, 'draws')
@@ -91,8 +114,14 @@ class BatchedPointReachEnv(DeviceEnv):
         self._check_io(reward, (B,), self.dtype, 'reward')
         self._check_io(absorbing, (B,), torch.uint8, 'absorbing')
         self._check_io(last, (B,), torch.uint8, 'last')
-        _lib_point.check(self._lib.atacom_point_step(self._h, _ptr(actions), _ptr(draws), _ptr(obs), _ptr(reward),
-                                                     _ptr(absorbing), _ptr(last), self._stream()))
+        self._check_io(mask, (B,), torch.uint8, 'mask')
+        self._launch_step(actions, draws, obs, reward, absorbing, last, mask)
+
+    def observe_into(self, obs):
+        """The observation of the CURRENT state into obs [B, obs_dim]: the masked reset with a mask that selects nobody.
+        Enqueue-only (what GraphedRollout captures)."""
+        self._check_io(obs, (self.batch, self.obs_dim), self.dtype, 'obs')
+        _lib_point.check(self._lib.atacom_point_reset(self._h, _ptr(self._nobody()), None, _ptr(obs), self._stream()))
 
     def rollout(self, actions, draws=None, want_next_obs=True, out=None):
         """T env steps in one kernel launch.  actions [T, B, 2], draws (optional) [T, B, n_objects, 2]
@@ -200,6 +229,42 @@ class BatchedPointReachEnv(DeviceEnv):
         res = (C.c_double * 3)()
         _lib_point.check(self._lib.atacom_point_get_stats(self._h, C.byref(res), int(clear), self._stream()))
         return float(res[0]), float(res[1]), float(res[2])
+
+    def snapshot(self, out=None):
+        """Checkpoint of the WHOLE handle (atacom_point_vec_snapshot_save): the state, the step and episode counters as the
+        integers they are, and the constraint statistics, which get_state() leaves out -- an opaque uint8 tensor on the device;
+        `restore(image)` followed by the same calls reproduces the run and its get_constraints_logs() bit for bit.  One launch
+        on the current stream, no synchronisation: capturable."""
+        lib = self._vec_lib()
+        n = int(lib.atacom_point_vec_snapshot_bytes(self._h))
+        if n < 0:
+            _lib_point_vec.check(n)
+        if out is None:
+            out = torch.empty((n,), device=self.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or out.numel() < n or not self._on_my_device(out) or not out.is_contiguous():
+            raise ValueError("snapshot buffer must be a contiguous uint8 tensor of >= %d bytes on %s" % (n, self.device))
+        _lib_point_vec.check(lib.atacom_point_vec_snapshot_save(self._h, _ptr(out), self._stream()))
+        return out
+
+    def restore(self, image):
+        """Puts a snapshot() back, the generator key included (`cfg.seed` follows); horizon, time step, obstacle mode and
+        auto_reset stay this engine's.  The image's header is read back first (synchronises the current stream) and checked
+        against the engine before anything is written: an image of another n_objects, dtype, batch or format raises AtacomError
+        naming the field and leaves state, statistics and key as they were."""
+        lib = self._vec_lib()
+        if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.numel() < 64 \
+                or not self._on_my_device(image) or not image.is_contiguous():
+            raise ValueError("snapshot image must be a contiguous uint8 tensor on %s" % (self.device,))
+        n = int(lib.atacom_point_vec_snapshot_bytes(self._h))
+        if n < 0:
+            _lib_point_vec.check(n)
+        # an image of another shape is refused here by its header, with the field named, before its size is looked at
+        seed = C.c_int32(0)
+        _lib_point_vec.check(lib.atacom_point_vec_snapshot_inspect(self._h, _ptr(image), C.byref(seed), self._stream()))
+        if image.numel() < n:
+            raise ValueError("snapshot image is truncated: %d bytes, %d expected" % (image.numel(), n))
+        _lib_point_vec.check(lib.atacom_point_vec_snapshot_restore(self._h, _ptr(image), self._stream()))
+        self.cfg.seed = int(seed.value)
 
     def get_state(self):
         """[B, 7 n + 8] = [observation, s, first-reset centres, _time, steps taken, episodes started, centres set]."""
