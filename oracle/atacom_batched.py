@@ -464,7 +464,7 @@ class BatchedAtacomEnv:
                 ddq = self.acc_truncation(dq_ctl, mu[:, :nq])
                 if sp.dynamics_mode >= 1:
                     ddq = self._rigid_body_substep(q_sim, dq_sim, ddq)
-                dq_sim = np.clip(dq_sim + ddq * sp.dt, -1.5 * sp.vel_max, 1.5 * sp.vel_max)
+                dq_sim = np.clip(dq_sim + ddq * sp.dt, -self.VEL_CLAMP * sp.vel_max, self.VEL_CLAMP * sp.vel_max)
                 q_sim = q_sim + dq_sim * sp.dt
             self.q, self.dq = q_sim, dq_sim
             m1 = mallet_xy_world(sp, self.q)
@@ -484,6 +484,8 @@ class BatchedAtacomEnv:
         self.t += 1
         return self.observation(), reward, absorbing, {}
 
+    VEL_CLAMP = 1.5           # the integrator's clamp in units of vel_max (a class attribute so that a CPU self-test can run
+                              # a deliberately wrong stand-in: tests/test_arm_limit_cases_oracle.py)
     SERVO_GAIN = 0.1          # PyBullet's default positionGain of POSITION_CONTROL (env_base.py:64-70)
     SERVO_EFFORT = np.array([40.0, 10.0, 10.0])      # urdf/iiwa_1.urdf:297,384,400: joint_7, striker_joint_1 / _2
 

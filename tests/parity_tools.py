@@ -64,7 +64,7 @@ def slice_env(o, idx):
     return p
 
 
-def perturbed(o, scale, rng, fields=('q', 'dq', 's', 'puck')):
+def perturbed(o, scale, rng, fields=('q', 'dq', 's', 'puck'), jc_noise=True):
     p = slice_env(o, np.arange(o.B))
     for k in ('decision_margin', 'contact_margin', 'cond_number', 'chart_skipped', 'chart_info', 'chart_default'):
         p.__dict__.pop(k, None)
@@ -75,7 +75,8 @@ def perturbed(o, scale, rng, fields=('q', 'dq', 's', 'puck')):
     # a float32 factorisation is exactly that, and the reference's LAPACK null basis responds to it with an amplification
     # of up to ~1e5 when joints sit near zero (nearly decoupled joint-limit rows: a near-breakdown of the Golub-Kahan
     # recurrence) -- see DESIGN.md section 2 and profiles/r02_parity_sensitivity.md
-    p.jc_noise = (scale * JC_NOISE_FRACTION, rng)
+    if jc_noise:
+        p.jc_noise = (scale * JC_NOISE_FRACTION, rng)
     return p
 
 
@@ -84,33 +85,64 @@ class SensitivityRecorder:
     explained (module docstring).
 
     step_fn(env_copy, inputs) -> [B, n_out] float64 array of everything that is compared (it may advance env_copy).
-    `inputs` is a tuple of float arrays that are perturbed together with the state (actions, noise)."""
+    `inputs` is a tuple of float arrays that are perturbed together with the state (actions, noise).
 
-    def __init__(self, step_fn, seed=0, state_fields=('q', 'dq', 's', 'puck')):
+    quick_scales / deep_scales / floor (defaults: the module's constants, the float32 rule) restate the rule for another
+    precision: the float64 build on ill-conditioned states is held to  err <= floor + C sens  with the probes scaled down
+    to float64-sized perturbations and jc_noise = False (no unstructured noise on J_c: `finish_float64`).
+    stacked_draws = True evaluates the draws of one scale as ONE oracle batch (every environment repeated `draws` times)
+    instead of one after the other: the same probes, drawn in another order, at a fraction of the cost where the oracle's
+    time is per call and not per environment (the deep probe of a few samples: 48 draws per scale).
+    repro_scales / repro_draws / repro_structured widen the DRAWS of the reproduction audit of errors above REPRO_ERR (its
+    REPRO_* constants stand): other scales than the deep ones, more draws per scale, and every scale also without the
+    unstructured J_c noise (J_c's structural zeros kept exact, as a device keeps them) -- tests/arm_limit_cases.py."""
+
+    def __init__(self, step_fn, seed=0, state_fields=('q', 'dq', 's', 'puck'), quick_scales=QUICK_SCALES,
+                 deep_scales=DEEP_SCALES, floor=FLOOR, jc_noise=True, stacked_draws=False, repro_scales=None, repro_draws=16,
+                 repro_structured=False):
         self.step_fn = step_fn
+        self.repro_scales, self.repro_draws, self.repro_structured = repro_scales, repro_draws, repro_structured
+        self.quick_scales, self.deep_scales, self.floor, self.jc_noise = quick_scales, deep_scales, floor, jc_noise
+        self.stacked = stacked_draws
         self.rng = np.random.default_rng(seed)
         self.fields = state_fields
         self.snaps, self.inputs, self.base, self.err, self.sens, self.where, self.dev = [], [], [], [], [], [], []
 
+    def _stacked(self, o, inputs, draws):
+        rep = np.repeat(np.arange(o.B), draws)
+        return slice_env(o, rep), tuple(x[rep] for x in inputs), rep
+
     def _sens(self, o, inputs, base, scales, draws):
         s = np.zeros(o.B)
+        if self.stacked:
+            big, bin_, rep = self._stacked(o, inputs, draws)
+            bb = base[rep]
+            for sc in scales:
+                p = perturbed(big, sc, self.rng, self.fields, self.jc_noise)
+                pin = tuple(x * (1.0 + sc * self.rng.choice([-1.0, 1.0], x.shape)) for x in bin_)
+                out = self.step_fn(p, pin)
+                r = (np.abs(out - bb) / np.maximum(1.0, np.abs(bb))).max(1)
+                s = np.maximum(s, r.reshape(o.B, draws).max(1))
+            return s
         for sc in scales:
             for _ in range(draws):
-                p = perturbed(o, sc, self.rng, self.fields)
+                p = perturbed(o, sc, self.rng, self.fields, self.jc_noise)
                 pin = tuple(x * (1.0 + sc * self.rng.choice([-1.0, 1.0], x.shape)) for x in inputs)
                 out = self.step_fn(p, pin)
                 s = np.maximum(s, (np.abs(out - base) / np.maximum(1.0, np.abs(base))).max(1))
         return s
 
-    def prepare(self, o, inputs):
+    def prepare(self, o, inputs, base=None):
         """Oracle side of one sample (independent of the device, so a test parametrised over kernel mappings prepares
-        once and compares many times).  Call BEFORE the oracle env `o` is stepped; returns the oracle outputs."""
+        once and compares many times).  Call BEFORE the oracle env `o` is stepped; returns the oracle outputs (`base`: those
+        outputs where another recorder of the same step_fn has already computed them)."""
         snap = slice_env(o, np.arange(o.B))
         for k in ('decision_margin', 'contact_margin', 'cond_number', 'chart_skipped', 'chart_info', 'chart_default'):
             snap.__dict__.pop(k, None)
-        base = self.step_fn(slice_env(snap, np.arange(o.B)), inputs)
+        if base is None:
+            base = self.step_fn(slice_env(snap, np.arange(o.B)), inputs)
         self.snaps.append(snap); self.inputs.append(inputs); self.base.append(base)
-        self.sens.append(self._sens(snap, inputs, base, QUICK_SCALES, 2))
+        self.sens.append(self._sens(snap, inputs, base, self.quick_scales, 2))
         return base
 
     def compare(self, t, dev_out):
@@ -138,6 +170,17 @@ class SensitivityRecorder:
         r.sens = [x.copy() for x in self.sens]
         return r
 
+    def head(self, n):
+        """fresh() restricted to the first n environments (a ragged device batch out of the same prepared samples)."""
+        r = copy.copy(self)
+        idx = np.arange(n)
+        r.snaps = [slice_env(s, idx) for s in self.snaps]
+        r.inputs = [tuple(x[:n] for x in i) for i in self.inputs]
+        r.base = [b[:n] for b in self.base]
+        r.sens = [s[:n].copy() for s in self.sens]
+        r.err, r.where, r.dev = [], [], []
+        return r
+
     def _unreproduced(self, E):
         """samples with E > REPRO_ERR that no perturbed oracle evaluation brings REPRO_GAIN x closer to the device"""
         big = np.argwhere(E > REPRO_ERR)
@@ -149,34 +192,73 @@ class SensitivityRecorder:
             dev = self.dev[t][idx]
             scale = np.maximum(1.0, np.abs(dev))
             best = np.full(len(idx), np.inf)
-            for sc in DEEP_SCALES:
-                for _ in range(16):
-                    p = perturbed(sub, sc, self.rng, self.fields)
-                    pin = tuple(x * (1.0 + sc * self.rng.choice([-1.0, 1.0], x.shape)) for x in sin)
-                    o = self.step_fn(p, pin)
-                    best = np.minimum(best, (np.abs(o - dev) / scale).max(1))
+            n = self.repro_draws
+            kinds = (self.jc_noise, False) if self.repro_structured and self.jc_noise else (self.jc_noise,)
+            if self.stacked:
+                stk, bin_, rep = self._stacked(sub, sin, n)
+            for sc in self.deep_scales if self.repro_scales is None else self.repro_scales:
+                for jc in kinds:
+                    if self.stacked:
+                        p = perturbed(stk, sc, self.rng, self.fields, jc)
+                        pin = tuple(x * (1.0 + sc * self.rng.choice([-1.0, 1.0], x.shape)) for x in bin_)
+                        r = (np.abs(self.step_fn(p, pin) - dev[rep]) / scale[rep]).max(1)
+                        best = np.minimum(best, r.reshape(len(idx), n).min(1))
+                        continue
+                    for _ in range(n):
+                        p = perturbed(sub, sc, self.rng, self.fields, jc)
+                        pin = tuple(x * (1.0 + sc * self.rng.choice([-1.0, 1.0], x.shape)) for x in sin)
+                        o = self.step_fn(p, pin)
+                        best = np.minimum(best, (np.abs(o - dev) / scale).max(1))
             for j, b in enumerate(idx):
                 if best[j] > E[t, b] / REPRO_GAIN:
                     out.append((int(t), int(b), float(E[t, b]), float(best[j])))
         return out, len(big)
 
-    def finish(self, what='', max_vacuous=0.4):
+    def _explain(self, limit=None):
+        """(E, S, unexplained, n_deep): the errors, the sensitivities after the deep probe of every sample that fails the
+        quick estimate, the samples that stay above  C sens + floor  as (t, env, err, sens, where), and how many samples
+        needed the deep probe.  limit (CPU self-tests only): deep-probe only the `limit` samples furthest above the quick
+        bound -- the others are neither explained nor reported."""
         E, S = np.array(self.err), np.array(self.sens)
-        bad = np.argwhere(E > C_SENS * S + FLOOR)
+        F = self.floor
+        bad = np.argwhere(E > C_SENS * S + F)
+        if limit is not None and len(bad) > limit:
+            over = (E / (C_SENS * S + F))[bad[:, 0], bad[:, 1]]
+            bad = bad[np.argsort(-over, kind='stable')[:limit]]
         n_deep = len(bad)
         unexplained = []
         for t in np.unique(bad[:, 0]) if n_deep else []:
             idx = bad[bad[:, 0] == t, 1]
             sub = slice_env(self.snaps[t], idx)
             sin = tuple(x[idx] for x in self.inputs[t])
-            s2 = self._sens(sub, sin, self.base[t][idx], DEEP_SCALES, 48)
+            s2 = self._sens(sub, sin, self.base[t][idx], self.deep_scales, 48)
             for j, b in enumerate(idx):
                 S[t, b] = max(S[t, b], s2[j])
-                if E[t, b] > C_SENS * S[t, b] + FLOOR:
+                if E[t, b] > C_SENS * S[t, b] + F:
                     unexplained.append((int(t), int(b), float(E[t, b]), float(S[t, b]), 'output %d' % self.where[t][b]))
-        ratio = E / (C_SENS * S + FLOOR)
-        self.bound = C_SENS * S + FLOOR                       # kept for followed_chart_errors
-        vac = float(np.mean(C_SENS * S + FLOOR > VACUOUS))
+        return E, S, unexplained, n_deep
+
+    def finish_float64(self, what='', max_loose=1.0):
+        """The float64 rule on ill-conditioned states (a recorder built with float64-sized scales and floor = the suite's
+        float64 bound): EVERY sample within  floor + C sens;  the share of samples whose allowance C sens exceeds the floor
+        itself (the bound is more than twice the suite's) is capped by max_loose."""
+        E, S, unexplained, n_deep = self._explain()
+        loose = float(np.mean(C_SENS * S > self.floor))
+        summary = ('%s: %d samples, err median %.2e / p99.9 %.2e / max %.2e; err / (%.0e + C sens) max %.2f; largest '
+                   'allowance %.2e; %d samples needed the deep probe; C sens > %.0e on %.2f %% of the samples (ceiling %.1f %%)'
+                   % (what, E.size, np.median(E), np.quantile(E, 0.999), E.max(), self.floor,
+                      (E / (C_SENS * S + self.floor)).max(), (C_SENS * S + self.floor).max(), n_deep, self.floor, 100 * loose,
+                      100 * max_loose))
+        assert np.isfinite(E).all(), 'non-finite errors: ' + summary
+        assert loose <= max_loose, 'the float64 allowance is loose on too many samples: ' + summary
+        assert not unexplained, 'UNEXPLAINED float64 errors (t, env, err, sens, where): %s | %s' % (unexplained[:10], summary)
+        return summary
+
+    def finish(self, what='', max_vacuous=0.4):
+        E, S, unexplained, n_deep = self._explain()
+        ratio = E / (C_SENS * S + self.floor)
+        self.bound = C_SENS * S + self.floor                  # kept for followed_chart_errors
+        vac = float(np.mean(self.bound > VACUOUS))
         summary = ('%s: %d samples, err median %.2e / p99.9 %.2e / max %.2e; err / (C sens + floor) max %.2f; '
                    '%d samples needed the deep probe; bound vacuous (> %.0e) on %.2f %% of the samples (ceiling %.1f %%)'
                    % (what, E.size, np.median(E), np.quantile(E, 0.999), E.max(), ratio.max(), n_deep, VACUOUS, 100 * vac,
