@@ -4,8 +4,9 @@
 Not part of the hot path: the reference trains with MushroomRL's PPO (examples/planar_air_hockey_exp.py,
 examples/iiwa_air_hockey_exp.py:137-170), which is not installed here.  This script shows the same loop shape on the
 engine: collection = ONE kernel launch per iteration (policy MLP + exploration noise + ATACOM env step fused,
-`rollout_policy`), policy / value update = plain torch autograd on the GPU.  Network = the reference's PPONetwork
-(examples/network.py:8-36: Linear-ReLU-Linear-ReLU-Linear, 64 units), Gaussian policy with state-independent std.
+`rollout_policy`), advantages = one more (`compute_gae`), policy / value update = plain torch autograd on the GPU.
+Network = the reference's PPONetwork (examples/network.py:8-36: Linear-ReLU-Linear-ReLU-Linear, 64 units), Gaussian policy with
+state-independent std.
 
     python examples/ppo_air_hockey.py --env planar --iters 60
 """
@@ -18,7 +19,7 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere in the checkout
-from rl_on_manifold_amd import BatchedAtacomEnv, MlpPolicy
+from rl_on_manifold_amd import BatchedAtacomEnv, MlpPolicy, compute_gae
 
 
 class Net(nn.Module):                      # same layer names as the reference's PPONetwork
@@ -73,15 +74,9 @@ def main():
         ab, last = d['absorbing'].bool(), d['last'].bool()
         with torch.no_grad():
             v, nv = critic(obs).squeeze(-1), critic(nobs).squeeze(-1)
-            nv = torch.where(ab, torch.zeros_like(nv), nv)
-            adv = torch.zeros_like(rew)
-            g = torch.zeros(B, device=dev)
-            for t in reversed(range(T)):
-                delta = rew[t] + gamma * nv[t] - v[t]
-                g = delta + gamma * lam * torch.where(last[t], torch.zeros_like(g), g)
-                adv[t] = g
-            ret = adv + v
-            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            # advantages, returns and PPO's normalisation: the recurrence over time is one kernel launch (returns.py), where a
+            # loop `for t in reversed(range(T))` costs five launches per step
+            ret, adv, _ = compute_gae(rew, ab, last, v, nv, gamma, lam, normalize=True)
             mu_old = actor(obs)
             logp_old = (-0.5 * ((act - mu_old) / log_std.exp()) ** 2 - log_std).sum(-1)
         flat = lambda x: x.reshape(T * B, *x.shape[2:])                       # noqa: E731

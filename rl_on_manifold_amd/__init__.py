@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ('RolloutCollector', 'RecordLayout', 'CompactRecordLayout'):
         from . import rollout
         return getattr(rollout, name)
+    if name in ('compute_gae', 'compute_J', 'episode_returns', 'normalize_advantages', 'gae_from_records', 'gae_from_compact'):
+        from . import returns
+        return getattr(returns, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

@@ -1,5 +1,5 @@
-"""The loader behind the ctypes binding modules (_lib, _lib_point, _lib_point_policy, _lib_point_compact, _lib_point_vec).  No
-numerics here.
+"""The loader behind the ctypes binding modules (_lib, _lib_point, _lib_point_policy, _lib_point_compact, _lib_point_vec,
+_lib_returns).  No numerics here.
 
 The libraries are the product: if one is missing or cannot be loaded, load() raises -- there is no CPU / PyTorch
 fallback anywhere in the package.

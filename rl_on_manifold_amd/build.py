@@ -5,7 +5,8 @@
 TARGETS below describes each library: libatacom_hip.so (the air-hockey and circle tasks), libatacom_point.so (the
 collision-avoidance task), libatacom_point_policy.so (its rollout with the actor network in the kernel),
 libatacom_point_compact.so (that rollout in the compact record format) and libatacom_point_vec.so (the task's masked step and
-checkpoint).  A library is one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
+checkpoint); beside the table, libatacom_returns.so (advantages and episode returns of a finished collection; its sources are in
+csrc_returns/).  A library is one translation unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into
 rl_on_manifold_amd/.  The .so files are git-ignored.
 """
 import os
@@ -29,7 +30,10 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 # paying for it (+29 % on the lane rollout kernel, r04_ab_sched_iterative_ilp.log; the option also crashes the compiler on
 # float64 instantiations).  (-amdgpu-sched-strategy=max-ilp was tried per unit in round 1 -- planar step kernel -4 %, planar
 # policy-rollout kernel +19 %, iiwa quad kernel +8 % -- and dropped, profiles/r01_lanes_vs_batch.md; round 5: +0.7 % on the headline)
-UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp']}
+# atacom_returns.hip: the fused multiply-adds of its recurrences are the explicit ones (include/atacom_returns_hip.h); the compiler
+# adds none
+UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
+              'atacom_returns.hip': ['-ffp-contract=off']}
 
 
 def _include(name):
@@ -82,6 +86,21 @@ LIB_POINT_VEC, UNITS_POINT_VEC = _POINT_VEC.lib, _POINT_VEC.units
 UNITS_POINT, UNITS_POINT_POLICY, UNITS_POINT_COMPACT = _POINT.units, _POINT_POLICY.units, _POINT_COMPACT.units
 
 
+# The post-processing of a collection (include/atacom_returns_hip.h) is a sixth library that belongs to no environment: it is
+# NOT an entry of TARGETS and its sources live in a directory of their own, so that _sources() of the five libraries above never
+# lists them.  It shares one header with them, the host scaffolding of csrc/atacom_capi_common.h.
+CSRC_RETURNS = os.path.join(HERE, 'csrc_returns')
+_RETURNS = Target(_lib_out('ATACOM_RETURNS_LIB_OUT', 'libatacom_returns.so'), ['atacom_returns.hip', 'atacom_returns_capi.cpp'],
+                  (), (), ('atacom_returns_hip.h',), False)
+LIB_RETURNS, UNITS_RETURNS = _RETURNS.lib, _RETURNS.units
+
+
+def _sources_returns():
+    """Everything in csrc_returns/, the shared host scaffolding and the public header."""
+    own = [os.path.join(CSRC_RETURNS, f) for f in os.listdir(CSRC_RETURNS) if f.endswith(('.h', '.hip', '.cpp'))]
+    return own + [os.path.join(CSRC, 'atacom_capi_common.h')] + [_include(h) for h in _RETURNS.headers]
+
+
 def _sources(target=_MAIN):
     """What a library is rebuilt for: its own units, every header of csrc/ that is not private to a library that does not
     feed it, and its public headers."""
@@ -110,7 +129,8 @@ def _stale(target):
     if not os.path.exists(target.lib):
         return True
     t = os.path.getmtime(target.lib)
-    return any(os.path.getmtime(p) > t for p in _sources(target))
+    sources = _sources_returns() if target is _RETURNS else _sources(target)
+    return any(os.path.getmtime(p) > t for p in sources)
 
 
 def needs_build():
@@ -133,17 +153,21 @@ def needs_build_point_vec():
     return _stale(_POINT_VEC)
 
 
+def needs_build_returns():
+    return _stale(_RETURNS)
+
+
 # kernel-tuning builds: ATACOM_KEEP_OBJ=1 keeps the objects of a build; ATACOM_ONLY_UNITS=a.hip,b.hip then recompiles only
 # those units (with ATACOM_HIPCC_FLAGS applied to them alone) and links against the kept objects of the others
 ONLY = [u for u in os.environ.get('ATACOM_ONLY_UNITS', '').split(',') if u]
 
 
-def _compile(target, unit):
-    src = os.path.join(CSRC, unit)
+def _compile(target, unit, csrc=CSRC):
+    src = os.path.join(csrc, unit)
     tag = os.environ.get('ATACOM_OBJ_TAG', '')
-    obj = os.path.join(CSRC, os.path.splitext(unit)[0] + tag + '.o')
+    obj = os.path.join(csrc, os.path.splitext(unit)[0] + tag + '.o')
     if ONLY and target.tuning and unit not in ONLY:
-        kept = os.path.join(CSRC, os.path.splitext(unit)[0] + os.environ.get('ATACOM_BASE_TAG', '_keep') + '.o')
+        kept = os.path.join(csrc, os.path.splitext(unit)[0] + os.environ.get('ATACOM_BASE_TAG', '_keep') + '.o')
         if not os.path.exists(kept):
             raise RuntimeError('ATACOM_ONLY_UNITS needs the kept object %s (build once with ATACOM_KEEP_OBJ=1 ATACOM_OBJ_TAG=_keep)' % kept)
         return kept
@@ -169,13 +193,13 @@ def _hipcc_version():
         return 'unavailable (%s)' % e
 
 
-def _build(target, force, verbose):
+def _build(target, force, verbose, csrc=CSRC):
     if not force and not _stale(target):
         return target.lib
     if verbose:
         print('[atacom] building %s for %s ...' % (os.path.basename(target.lib), ARCH), flush=True)
     with ThreadPoolExecutor(max_workers=min(len(target.units), os.cpu_count() or 4)) as ex:
-        objs = list(ex.map(lambda u: _compile(target, u), target.units))
+        objs = list(ex.map(lambda u: _compile(target, u, csrc), target.units))
     cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', target.lib] + objs
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -217,8 +241,13 @@ def build_point_vec(force=False, verbose=True):
     return _build(_POINT_VEC, force, verbose)
 
 
+def build_returns(force=False, verbose=True):
+    """libatacom_returns.so: two units, a few seconds."""
+    return _build(_RETURNS, force, verbose, CSRC_RETURNS)
+
+
 if __name__ == '__main__':
-    for _b in (build, build_point, build_point_policy, build_point_compact, build_point_vec):
+    for _b in (build, build_point, build_point_policy, build_point_compact, build_point_vec, build_returns):
         _b(force='--force' in sys.argv)
-    for _t in TARGETS.values():
+    for _t in list(TARGETS.values()) + [_RETURNS]:
         print(_t.lib)

@@ -63,6 +63,12 @@ def unpack_fields(rec, fields):
     return out
 
 
+def record_columns(rec, fields):
+    """Views (no copy) of `fields` into records [..., F] as they are stored: the two flags keep the records' dtype (0.0 / 1.0)
+    and their stride, which is how the kernels of returns.py read them in place."""
+    return {name: rec[..., ix] for name, ix in fields.items()}
+
+
 def pack_fields(rec, fields, values):
     """Write `values` (one array per field, in record order; flags of any dtype) into the fields of rec [..., F]."""
     for ix, v in zip(fields.values(), values):
