@@ -16,10 +16,11 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+from rl_on_manifold_amd import build                  # noqa: E402
 from test_kernel_resources import LLVM, _kernels      # noqa: E402
 
-LIBS = ('libatacom_hip.so', 'libatacom_point.so', 'libatacom_point_policy.so')
+LIBS = tuple(os.path.basename(t.lib) for t in build.TARGETS.values())     # the file names that build.py writes
 
 
 def _readelf(flag, elf):

@@ -9,23 +9,13 @@ import numpy as np
 
 from oracle import atacom_scalar as osc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared_functions():
-    src = open(os.path.join(ROOT, 'include', 'atacom_hip.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(atacom_[a-z_]+)\s*\(', src)))
+import abi_tools as abi
+from abi_tools import ROOT
 
 
 def test_library_exports_every_declared_symbol(lib_built):
     from rl_on_manifold_amd import _lib
-    names = _declared_functions()
-    assert len(names) >= 14
-    lib = ctypes.CDLL(lib_built)
-    for n in names:
-        assert hasattr(lib, n), n
-    assert sorted(_lib.EXPORTS) == names
+    assert len(abi.one_symbol_set(lib_built, 'atacom_hip.h', 'atacom_', _lib)) >= 14
     assert _lib.load().atacom_version().startswith(b'atacom_hip')
 
 

@@ -1,72 +1,41 @@
 """CPU-only checks of libatacom_returns.so, the post-processing of a collection (advantages, normalisation, episode returns): the
 header is plain C11, the declared symbols are exactly the exported ones and the ctypes table, every argument rule is enforced
 without a GPU and with a message, no kernel uses scratch and only the reduction stage uses LDS, the exec-mask audit finds
-nothing, the five other libraries' build table and source directory are what they were, staleness follows the directory split,
-and the Python signatures are the documented ones.  No compute call is made (no GPU here)."""
+nothing and the Python signatures are the documented ones.  No compute call is made (no GPU here)."""
 import ctypes
 import inspect
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_kernel_resources import LLVM, _kernels        # noqa: E402
+import abi_tools as abi
 
-HEADER = os.path.join(ROOT, 'include', 'atacom_returns_hip.h')
 FUNCTIONS = ('version', 'last_error', 'gae', 'normalize', 'episodes')
-OWN = {'atacom_returns.h', 'atacom_returns.hip', 'atacom_returns_capi.cpp'}
-CSRC_FILES = """
-atacom_capi.cpp atacom_capi_common.h atacom_chart.h atacom_chart.hip atacom_chart_group.h atacom_chart_iiwa.hip
-atacom_circle.hip atacom_dynamics.h atacom_dynamics_link.h atacom_envs.h atacom_iiwa.hip atacom_iiwa_dyn.hip
-atacom_iiwa_dyn_chart.hip atacom_iiwa_dyn_f64.hip atacom_iiwa_f64.hip atacom_iiwa_group.h atacom_iiwa_group.hip
-atacom_iiwa_inertia.h atacom_kernels.h atacom_linalg.h atacom_mlp_host.h atacom_noise_iiwa.hip atacom_noise_iiwa_f64.hip
-atacom_noise_planar.hip atacom_ops.h atacom_ops_impl.h atacom_planar.hip atacom_point.h atacom_point.hip
-atacom_point_capi.cpp atacom_point_compact.h atacom_point_compact.hip atacom_point_compact_capi.cpp
-atacom_point_compact_ops.h atacom_point_handle.h atacom_point_ops.h atacom_point_policy.h atacom_point_policy.hip
-atacom_point_policy_capi.cpp atacom_point_policy_ops.h atacom_point_vec.h atacom_point_vec.hip atacom_point_vec_capi.cpp
-atacom_point_vec_ops.h atacom_policy.h atacom_quad.h
-""".split()
 
 
 @pytest.fixture(scope='module')
 def returns_lib():
     from rl_on_manifold_amd import build
-    return build.build_returns(verbose=False)
-
-
-def _declared_functions():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(atacom_returns_[a-z_]+)\s*\(', src)))
+    return build.build('returns', verbose=False)
 
 
 def test_header_is_plain_c11(tmp_path):
-    src = tmp_path / 'use.c'
-    src.write_text('#include "atacom_returns_hip.h"\n'
-                   'int main(void) {\n'
-                   '    atacom_returns_gae_args g = {0}; atacom_returns_normalize_args n = {0}; atacom_returns_episodes_args e = {0};\n'
-                   '    g.struct_size = sizeof g; n.struct_size = sizeof n; e.struct_size = sizeof e;\n'
-                   '    if (ATACOM_RETURNS_WORKSPACE_DOUBLES(3, 5) != 3 * (15 + 256)) return 1;\n'
-                   '    if (atacom_returns_gae(&g) == ATACOM_RETURNS_OK) return 2;\n'
-                   '    if (atacom_returns_normalize(&n) == ATACOM_RETURNS_OK) return 3;\n'
-                   '    return atacom_returns_episodes(&e) == ATACOM_RETURNS_OK || !atacom_returns_version() || !atacom_returns_last_error(); }\n')
-    subprocess.check_call(['gcc', '-std=c11', '-pedantic', '-Wall', '-Werror', '-I', os.path.dirname(HEADER), '-c', str(src),
-                           '-o', str(tmp_path / 'use.o')])
+    abi.compile_c11(tmp_path, abi.INCLUDE, '#include "atacom_returns_hip.h"\n'
+                    'int main(void) {\n'
+                    '    atacom_returns_gae_args g = {0}; atacom_returns_normalize_args n = {0}; atacom_returns_episodes_args e = {0};\n'
+                    '    g.struct_size = sizeof g; n.struct_size = sizeof n; e.struct_size = sizeof e;\n'
+                    '    if (ATACOM_RETURNS_WORKSPACE_DOUBLES(3, 5) != 3 * (15 + 256)) return 1;\n'
+                    '    if (atacom_returns_gae(&g) == ATACOM_RETURNS_OK) return 2;\n'
+                    '    if (atacom_returns_normalize(&n) == ATACOM_RETURNS_OK) return 3;\n'
+                    '    return atacom_returns_episodes(&e) == ATACOM_RETURNS_OK || !atacom_returns_version() || !atacom_returns_last_error(); }\n')
 
 
 def test_declared_exported_and_bound_symbols_are_one_set(returns_lib):
     from rl_on_manifold_amd import _lib_returns
-    names = _declared_functions()
+    names = abi.one_symbol_set(returns_lib, 'atacom_returns_hip.h', 'atacom_returns_', _lib_returns)
     assert names == sorted('atacom_returns_' + n for n in FUNCTIONS)
-    nm = os.path.join(LLVM, 'llvm-nm')
-    out = subprocess.run([nm if os.path.exists(nm) else 'nm', '-D', '--defined-only', returns_lib], capture_output=True,
-                         text=True, check=True).stdout
-    exported = sorted(ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith('atacom_'))
-    assert exported == names, exported
-    assert sorted(_lib_returns.EXPORTS) == names
     assert _lib_returns.load().atacom_returns_version().startswith(b'atacom_returns')
 
 
@@ -80,7 +49,7 @@ def test_the_ctypes_structs_have_the_layout_of_the_header(tmp_path):
                    '    offsetof(atacom_returns_normalize_args, stream), sizeof(atacom_returns_episodes_args),\n'
                    '    offsetof(atacom_returns_episodes_args, stream)); return 0; }\n')
     exe = str(tmp_path / 'layout')
-    subprocess.check_call(['gcc', '-std=c11', '-I', os.path.dirname(HEADER), str(src), '-o', exe])
+    subprocess.check_call(['gcc', '-std=c11', '-I', abi.INCLUDE, str(src), '-o', exe])
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     assert got == [ctypes.sizeof(lr.View), ctypes.sizeof(lr.Shape), ctypes.sizeof(lr.GaeArgs), lr.GaeArgs.stream.offset,
                    ctypes.sizeof(lr.NormalizeArgs), lr.NormalizeArgs.stream.offset, ctypes.sizeof(lr.EpisodesArgs),
@@ -170,44 +139,33 @@ def test_python_arguments_are_refused_before_the_library_is_called():
             call()
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, 'llvm-readelf')), reason='needs the ROCm LLVM binutils')
+@abi.needs_llvm('llvm-readelf')
 def test_kernel_census_and_resources(returns_lib, tmp_path):
-    ks = _kernels(str(tmp_path), so=returns_lib)
-    names = sorted(k[0].replace('atacom_returns::', '') for k in ks)
+    ks = abi.kernel_rows(returns_lib, tmp_path)
     flags = {'float': ('float', 'unsigned char'), 'double': ('double', 'unsigned char')}
     want = ['k_returns_gae<%s, %s, %s>' % (e, f, v) for e in flags for f in flags[e] for v in ('false', 'true')] + \
            ['k_returns_episodes<%s, %s>' % (e, f) for e in flags for f in flags[e]] + \
            ['k_returns_%s<%s>' % (k, e) for k in ('lane_stats', 'normalize') for e in flags] + \
            ['k_returns_reduce_partial', 'k_returns_reduce_final<false>', 'k_returns_reduce_final<true>']
-    assert names == sorted(want), names
-    table = []
-    for name, lds, scratch, vgpr, agpr, code in sorted(ks):
-        name = name.replace('atacom_returns::', '')
-        table.append('%-44s VGPR %3d AGPR %2d scratch %d LDS %d code %d' % (name, vgpr, agpr, scratch, lds, code))
+    assert [k[0] for k in ks] == sorted(want), ks
+    for name, lds, scratch, vgpr, agpr, code in ks:
+        print('%-44s VGPR %3d AGPR %2d scratch %d LDS %d code %d' % (name, vgpr, agpr, scratch, lds, code))
         assert scratch == 0, (name, scratch)
-        if name.startswith('k_returns_reduce'):
-            assert lds == 3 * 256 * 8, (name, lds)
-        else:
-            assert lds == 0, (name, lds)
-    print('\n'.join(table))
+        assert lds == (3 * 256 * 8 if name.startswith('k_returns_reduce') else 0), (name, lds)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, 'llvm-objdump')), reason='needs the ROCm LLVM binutils')
+@abi.needs_llvm('llvm-objdump')
 def test_the_scan_kernels_have_no_barrier_and_only_the_explicit_fused_operations(returns_lib, tmp_path):
     """No s_barrier in a scan kernel, and as many fused multiply-adds as the header writes down per step: two per
     step in the advantage kernels (kDepth unrolled steps), one in the episode kernels -- the compiler added none."""
-    _kernels(str(tmp_path), so=returns_lib)          # leaves the code object in tmp_path
-    elf = [os.path.join(str(tmp_path), f) for f in os.listdir(str(tmp_path)) if f.endswith('.elf')]
-    assert len(elf) == 1
-    dis = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--demangle', elf[0]], capture_output=True, text=True,
-                         check=True).stdout
+    bodies = abi.function_bodies(returns_lib, tmp_path)
+    assert len({elf for elf, _, _ in bodies}) == 1
     # the depth this build was compiled with: the header's default unless ATACOM_HIPCC_FLAGS overrides it
-    header = open(os.path.join(ROOT, 'rl_on_manifold_amd', 'csrc_returns', 'atacom_returns.h')).read()
+    header = open(os.path.join(abi.ROOT, 'rl_on_manifold_amd', 'csrc_returns', 'atacom_returns.h')).read()
     override = re.search(r'-DATACOM_RETURNS_DEPTH=(\d+)', os.environ.get('ATACOM_HIPCC_FLAGS', ''))
     depth = int((override or re.search(r'define ATACOM_RETURNS_DEPTH (\d+)', header)).group(1))
     seen = 0
-    for body in re.split(r'\n(?=[0-9a-f]+ <)', dis):
-        head = body.split('\n', 1)[0]
+    for _, head, body in bodies:
         scan = re.search(r'k_returns_(gae|episodes|lane_stats)<(.*)>', head)
         if not scan:
             continue
@@ -220,46 +178,7 @@ def test_the_scan_kernels_have_no_barrier_and_only_the_explicit_fused_operations
 
 
 def test_exec_mask_audit_finds_nothing(returns_lib):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'profiles', 'tools', 'exec_restore_audit.py'), '--so', returns_lib],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert ' 0 copies' in r.stdout, r.stdout
-
-
-def test_the_other_libraries_build_table_and_sources_are_what_they_were():
-    from rl_on_manifold_amd import build
-    assert list(build.TARGETS) == ['hip', 'point', 'point_policy', 'point_compact', 'point_vec']
-    assert len(build.UNITS) == 14 and build.UNITS[0] == 'atacom_iiwa.hip' and build.UNITS[-1] == 'atacom_capi.cpp'
-    assert not any('returns' in u for t in build.TARGETS.values() for u in t.units)
-    sources = sorted(f for f in os.listdir(build.CSRC) if f.endswith(('.h', '.hip', '.cpp')))
-    assert sources == sorted(CSRC_FILES)
-    assert sorted(f for f in os.listdir(build.CSRC_RETURNS) if f.endswith(('.h', '.hip', '.cpp'))) == sorted(OWN)
-    assert build.UNITS_RETURNS == ['atacom_returns.hip', 'atacom_returns_capi.cpp']
-    assert os.path.basename(build.LIB_RETURNS) == 'libatacom_returns.so' or os.environ.get('ATACOM_RETURNS_LIB_OUT')
-    for t in build.TARGETS.values():
-        assert not any('returns' in os.path.basename(p) for p in build._sources(t))
-    assert {os.path.basename(p) for p in build._sources_returns()} == OWN | {'atacom_capi_common.h', 'atacom_returns_hip.h'}
-
-
-def test_a_touched_file_makes_exactly_the_libraries_that_include_it_stale(monkeypatch):
-    from rl_on_manifold_amd import build
-    libs = (build.LIB, build.LIB_POINT, build.LIB_POINT_POLICY, build.LIB_POINT_COMPACT, build.LIB_POINT_VEC, build.LIB_RETURNS)
-    touched = []
-    real_exists = os.path.exists
-    monkeypatch.setattr(build.os.path, 'exists', lambda p: p in libs or real_exists(p))
-    monkeypatch.setattr(build.os.path, 'getmtime', lambda p: 2.0 if os.path.basename(p) in touched else 1.0)
-
-    def stale():
-        return [build.needs_build(), build.needs_build_point(), build.needs_build_point_policy(), build.needs_build_point_compact(),
-                build.needs_build_point_vec(), build.needs_build_returns()]
-
-    assert stale() == [False] * 6
-    only_mine = [False] * 5 + [True]
-    for name, want in (('atacom_returns.h', only_mine), ('atacom_returns.hip', only_mine), ('atacom_returns_capi.cpp', only_mine),
-                       ('atacom_returns_hip.h', only_mine), ('atacom_capi_common.h', [True] * 6),
-                       ('atacom_kernels.h', [True] * 5 + [False]), ('atacom_point_hip.h', [False, True, True, True, True, False])):
-        touched[:] = [name]
-        assert stale() == want, name
+    abi.exec_audit(returns_lib)
 
 
 def test_python_surface():
