@@ -3,14 +3,17 @@
 
 Not part of the hot path: the reference trains with MushroomRL's PPO (examples/planar_air_hockey_exp.py,
 examples/iiwa_air_hockey_exp.py:137-170), which is not installed here.  This script shows the same loop shape on the
-engine: collection = ONE kernel launch per iteration (policy MLP + exploration noise + ATACOM env step fused,
-`rollout_policy`), advantages = one more (`compute_gae`), policy / value update = plain torch autograd on the GPU.
+engine: collection = ONE kernel launch per iteration (policy MLP + exploration noise + ATACOM env step fused, written as packed
+records: `rollout_packed`), the critic on obs and next_obs and the log-probability of the drawn actions = three more, read from
+the records in place (`values_from_records`, `log_prob_from_records`), advantages = one more (`gae_from_records`), policy /
+value update = plain torch autograd on the GPU.
 Network = the reference's PPONetwork (examples/network.py:8-36: Linear-ReLU-Linear-ReLU-Linear, 64 units), Gaussian policy with
 state-independent std.
 
     python examples/ppo_air_hockey.py --env planar --iters 60
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -19,7 +22,8 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere in the checkout
-from rl_on_manifold_amd import BatchedAtacomEnv, MlpPolicy, compute_gae
+from rl_on_manifold_amd import (BatchedAtacomEnv, MlpPolicy, RecordLayout, gae_from_records, log_prob_from_records,
+                                values_from_records)
 
 
 class Net(nn.Module):                      # same layer names as the reference's PPONetwork
@@ -58,27 +62,29 @@ def main():
     opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
     gamma, lam, clip, epochs, mb = 0.99, 0.95, 0.2, 4, 16384
     norm = lambda o: (o - shift) * scale                                     # noqa: E731
+    lay = RecordLayout([B], D, k)
+    log_norm = 0.5 * k * math.log(2.0 * math.pi)                              # the Gaussian's constant, as log_prob_from_records has it
     t_collect = t_fit = 0.0
     for it in range(args.iters):
         t0 = time.perf_counter()
-        pol = MlpPolicy.from_module(actor, std=log_std.detach().exp())
-        pol.tensors['obs_shift'], pol.tensors['obs_scale'] = shift, scale
+        pol, cri = MlpPolicy.from_module(actor, std=log_std.detach().exp()), MlpPolicy.from_module(critic)
+        for net in (pol, cri):
+            net.tensors['obs_shift'], net.tensors['obs_scale'] = shift, scale
         noise = torch.randn((T, B, k), device=dev)
         env.reset()
-        d = env.rollout_policy(pol, T, noise=noise)                           # ONE launch: T steps of B envs
+        rec = env.rollout_packed(policy=pol, n_steps=T, noise=noise)          # ONE launch: T steps of B envs, [T, B, 2 D + k + 3]
         c_avg, c_max, c_dq = env.get_constraints_logs()
         torch.cuda.synchronize()
         t_collect += time.perf_counter() - t0
         t0 = time.perf_counter()
-        obs, nobs, act, rew = norm(d['obs']), norm(d['next_obs']), d['action'], d['reward']
-        ab, last = d['absorbing'].bool(), d['last'].bool()
-        with torch.no_grad():
-            v, nv = critic(obs).squeeze(-1), critic(nobs).squeeze(-1)
-            # advantages, returns and PPO's normalisation: the recurrence over time is one kernel launch (returns.py), where a
-            # loop `for t in reversed(range(T))` costs five launches per step
-            ret, adv, _ = compute_gae(rew, ab, last, v, nv, gamma, lam, normalize=True)
-            mu_old = actor(obs)
-            logp_old = (-0.5 * ((act - mu_old) / log_std.exp()) ** 2 - log_std).sum(-1)
+        # what the update needs from the old networks, each one launch over the records where they lie (evaluate.py): V(obs) and
+        # V(next_obs), the log-probability of the drawn actions -- and then advantages, returns and PPO's normalisation, the
+        # recurrence over time in one launch (returns.py), where a loop `for t in reversed(range(T))` costs five per step
+        v, nv = values_from_records(lay, rec, cri)
+        ret, adv, _ = gae_from_records(lay, rec, v, nv, gamma, lam, normalize=True)
+        logp_old = log_prob_from_records(lay, rec, pol)
+        d = lay.unpack(rec)
+        obs, act, rew, last = norm(d['obs']), d['action'], d['reward'], d['last']
         flat = lambda x: x.reshape(T * B, *x.shape[2:])                       # noqa: E731
         fo, fa, fadv, fret, flp = flat(obs), flat(act), flat(adv), flat(ret), flat(logp_old)
         for _ in range(epochs):
@@ -86,7 +92,7 @@ def main():
             for i in range(0, T * B, mb):
                 idx = perm[i:i + mb]
                 mu = actor(fo[idx])
-                logp = (-0.5 * ((fa[idx] - mu) / log_std.exp()) ** 2 - log_std).sum(-1)
+                logp = (-0.5 * ((fa[idx] - mu) / log_std.exp()) ** 2 - log_std).sum(-1) - log_norm
                 ratio = (logp - flp[idx]).exp()
                 pl = -torch.min(ratio * fadv[idx], ratio.clamp(1 - clip, 1 + clip) * fadv[idx]).mean()
                 vl = (critic(fo[idx]).squeeze(-1) - fret[idx]).pow(2).mean()
@@ -97,7 +103,7 @@ def main():
         t_fit += time.perf_counter() - t0
         ep_ret = rew.sum(0).mean().item() if not last[:-1].any() else (rew.sum() / last.sum().clamp_min(1)).item()
         goals = ((rew > 70) if args.task == 'H' else (rew < -40)).sum().item()      # task 'D': goals CONCEDED
-        hits = (d['reward'] > 0.99).any(0).float().mean().item()
+        hits = (rew > 0.99).any(0).float().mean().item()
         print('iter %3d  return/episode %8.3f  goals %5d  frac envs with a hit %.3f  c_max %.4f  c_dq_max %.4f  std %.3f'
               % (it, ep_ret, goals, hits, c_max, c_dq, log_std.exp().mean().item()), flush=True)
     print('collection %.2f s (%.3g env-steps/s incl. policy), fitting %.2f s' % (

@@ -24,6 +24,10 @@ def __getattr__(name):
     if name in ('compute_gae', 'compute_J', 'episode_returns', 'normalize_advantages', 'gae_from_records', 'gae_from_compact'):
         from . import returns
         return getattr(returns, name)
+    if name in ('evaluate_mlp', 'gaussian_log_prob', 'values_from_records', 'values_from_compact', 'log_prob_from_records',
+                'evaluate_rows'):
+        from . import evaluate
+        return getattr(evaluate, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

@@ -604,6 +604,37 @@ class MlpPolicy:
             m.ou_state = self._ou_state_for(env).data_ptr()
         return m
 
+    def as_struct_on(self, device, dtype):
+        """The atacom_mlp of this network for a call that has no environment (evaluate.py): the weights, the observation
+        normalisation and std on `device` in `dtype`.  Tensors that are already there are used as they are (no copy, so the call
+        can be captured in a graph); the copies live as long as the policy or until the next call.  The exploration options
+        travel as they are set -- the library refuses what it does not evaluate -- except the Ornstein-Uhlenbeck state, which
+        belongs to an environment's batch and is refused here."""
+        if self.explore == _lib.EXPLORE_OU:
+            raise ValueError("a DDPG policy carries per-environment noise state: it cannot be evaluated without its environment")
+        device = torch.device(device)
+        dev = {k: (None if v is None else torch.as_tensor(v).detach().to(device=device, dtype=dtype).contiguous())
+               for k, v in self.tensors.items()}
+        self._keep = dev
+        m = _lib.AtacomMlp()
+        m.struct_size = C.sizeof(_lib.AtacomMlp)
+        if dev['W1'].dim() != 2 or dev['W2'].dim() != 2 or dev['W3'].dim() != 2:
+            raise ValueError("expected Linear(n_in,h) - Linear(h,h) - Linear(h,n_out)")
+        m.n_in, m.hidden, m.n_out = dev['W1'].shape[1], dev['W1'].shape[0], dev['W3'].shape[0]
+        if tuple(dev['W2'].shape) != (m.hidden, m.hidden) or dev['W3'].shape[1] != m.hidden:
+            raise ValueError("expected Linear(n_in,h) - Linear(h,h) - Linear(h,n_out)")
+        for k, n in (('b1', m.hidden), ('b2', m.hidden), ('b3', m.n_out), ('obs_shift', m.n_in), ('obs_scale', m.n_in), ('std', m.n_out)):
+            if dev.get(k) is not None and dev[k].numel() != n:
+                raise ValueError("%s holds %d values where the network needs %d" % (k, dev[k].numel(), n))
+        m.activation = self.activation
+        for k in ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'obs_shift', 'obs_scale', 'std', 'sW1', 'sb1', 'sW2', 'sb2',
+                  'sW3', 'sb3', 'act_scale', 'act_low', 'act_high'):
+            v = dev.get(k)
+            setattr(m, k, None if v is None else v.data_ptr())
+        m.squash, m.log_std_min, m.log_std_max = int(self.squash), self.log_std_min, self.log_std_max
+        m.mean_mode, m.explore = self.mean_mode, self.explore
+        return m
+
 
 # ---------------------------------------------------------------------- stand-alone primitives
 @contextlib.contextmanager
