@@ -20,7 +20,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 from rl_on_manifold_amd import build                  # noqa: E402
 from test_kernel_resources import LLVM, _kernels      # noqa: E402
 
-LIBS = tuple(os.path.basename(t.lib) for t in build.TARGETS.values())     # the file names that build.py writes
+LIBS = tuple(build.naming(name).file for name in build.TARGETS)      # every library of the table, by the name build.py gives it
 
 
 def _readelf(flag, elf):

@@ -1,15 +1,39 @@
-"""The loader behind the ctypes binding modules (_lib, _lib_point, _lib_point_policy, _lib_point_compact, _lib_point_vec,
-_lib_returns).  No numerics here.
+"""What the ctypes binding modules share: one per row of build.TARGETS, named naming(key).binding.  A binding module
+holds its structs, its SIGNATURES and the constants of its header; library() gives it the rest.  No numerics here.
 
 The libraries are the product: if one is missing or cannot be loaded, load() raises -- there is no CPU / PyTorch
 fallback anywhere in the package.
 """
 import ctypes as C
 import os
+from collections import namedtuple
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+Names = namedtuple('Names', 'file env symbols binding')
+
+
+def naming(key):
+    """What is spelled after a library's key in build.TARGETS: its file name; its environment variable, which redirects what
+    the binding loads (with _OUT appended: where build.py writes); the prefix of its C symbols; the module that binds it.
+    The main library, `hip`, predates the others and has no infix."""
+    infix = '' if key == 'hip' else key + '_'
+    return Names('libatacom_%s.so' % key, 'ATACOM_%sLIB' % infix.upper(), 'atacom_' + infix, ('_lib_' + infix).rstrip('_'))
+
+
+# the status codes and dtype tags of every public header (ATACOM_*_OK ..., ATACOM_*_F32 / F64)
+OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
+F32, F64 = 0, 1
 
 
 class AtacomError(RuntimeError):
     pass
+
+
+def new_args(cls):
+    """A zeroed argument struct with its struct_size filled in."""
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    return a
 
 
 _loaded = {}
@@ -40,9 +64,18 @@ def load(path, name, signatures):
     return lib
 
 
-def checker(load_lib, last_error):
-    """check(rc) of one library: raises AtacomError with the text of its `last_error` function for a non-zero code."""
+def library(key, signatures):
+    """(LIB_PATH, load, check) of the library `key` of build.TARGETS.  The path is the library's file next to this module unless
+    its environment variable points at an alternative build of it (kernel-tuning experiments do); load() loads it once with
+    `signatures` applied and raises if it is not built; check(rc) raises AtacomError with the text of the library's
+    last_error function for a non-zero code."""
+    n = naming(key)
+    path = os.environ.get(n.env) or os.path.join(HERE, n.file)
+
+    def load_lib():
+        return load(path, n.file, signatures)
+
     def check(rc):
         if rc != 0:
-            raise AtacomError(getattr(load_lib(), last_error)().decode())
-    return check
+            raise AtacomError(getattr(load_lib(), n.symbols + 'last_error')().decode())
+    return path, load_lib, check

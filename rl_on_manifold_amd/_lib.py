@@ -4,18 +4,11 @@ The library is the product: if it is missing or cannot be loaded this module rai
 CPU / PyTorch fallback anywhere in the package.
 """
 import ctypes as C
-import os
 
 from . import _binding
-from ._binding import AtacomError  # noqa: F401
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-# ATACOM_LIB lets kernel-tuning experiments point at an alternative build of the same library
-LIB_PATH = os.environ.get('ATACOM_LIB') or os.path.join(HERE, 'libatacom_hip.so')
+from ._binding import AtacomError, OK, E_INVALID, E_HIP, E_UNSUPPORTED, F32, F64  # noqa: F401
 
 ENV_CIRCLE, ENV_PLANAR, ENV_IIWA, ENV_CIRCLE_EC, ENV_CIRCLE_T = 0, 1, 2, 3, 4
-F32, F64 = 0, 1
-OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
 MAX_C, MAX_Q = 12, 6
 
 
@@ -97,14 +90,7 @@ SIGNATURES = {
     'atacom_constraint_terms': (_int, [_cfg, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
-
-
-def load():
-    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    return _binding.load(LIB_PATH, 'libatacom_hip.so', SIGNATURES)
-
-
-check = _binding.checker(load, 'atacom_last_error')
+LIB_PATH, load, check = _binding.library('hip', SIGNATURES)
 
 
 def default_config(env_id):

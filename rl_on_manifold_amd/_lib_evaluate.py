@@ -5,17 +5,11 @@ struct.  No numerics here.
 Like _lib.py: if the library is missing or cannot be loaded this module raises -- there is no CPU / PyTorch fallback.
 """
 import ctypes as C
-import os
 
 from . import _binding
-from ._binding import AtacomError  # noqa: F401
+from ._binding import AtacomError, OK, E_INVALID, E_HIP, E_UNSUPPORTED, F32, F64  # noqa: F401
 from ._lib import AtacomMlp
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('ATACOM_EVALUATE_LIB') or os.path.join(HERE, 'libatacom_evaluate.so')
-
-OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
-F32, F64 = 0, 1
 MAX_IN, MAX_OUT, HIDDEN, MAX_BLOCKS = 32, 8, 64, 65535
 
 
@@ -30,10 +24,7 @@ class EvaluateArgs(C.Structure):
 
 
 def new_args(cls=EvaluateArgs):
-    """A zeroed argument struct with its struct_size filled in."""
-    a = cls()
-    a.struct_size = C.sizeof(cls)
-    return a
+    return _binding.new_args(cls)                     # the one call of this library: its struct is the default
 
 
 _int = C.c_int
@@ -44,11 +35,4 @@ SIGNATURES = {
     'atacom_evaluate_mlp': (_int, [C.POINTER(EvaluateArgs)]),
 }
 EXPORTS = list(SIGNATURES)
-
-
-def load():
-    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    return _binding.load(LIB_PATH, 'libatacom_evaluate.so', SIGNATURES)
-
-
-check = _binding.checker(load, 'atacom_evaluate_last_error')
+LIB_PATH, load, check = _binding.library('evaluate', SIGNATURES)

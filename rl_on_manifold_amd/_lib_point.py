@@ -3,16 +3,9 @@
 Like _lib.py: if the library is missing or cannot be loaded this module raises -- there is no CPU / PyTorch fallback.
 """
 import ctypes as C
-import os
 
 from . import _binding
-from ._binding import AtacomError  # noqa: F401
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('ATACOM_POINT_LIB') or os.path.join(HERE, 'libatacom_point.so')
-
-F32, F64 = 0, 1
-OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
+from ._binding import AtacomError, OK, E_INVALID, E_HIP, E_UNSUPPORTED, F32, F64  # noqa: F401
 
 
 class AtacomPointConfig(C.Structure):
@@ -39,14 +32,7 @@ SIGNATURES = {
     'atacom_point_set_seed': (_int, [_vp, _i32]),
 }
 EXPORTS = list(SIGNATURES)
-
-
-def load():
-    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    return _binding.load(LIB_PATH, 'libatacom_point.so', SIGNATURES)
-
-
-check = _binding.checker(load, 'atacom_point_last_error')
+LIB_PATH, load, check = _binding.library('point', SIGNATURES)
 
 
 def default_config():

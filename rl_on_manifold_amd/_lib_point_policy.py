@@ -5,16 +5,10 @@ network description of the main library (_lib.AtacomMlp).  No numerics here.
 Like _lib.py: if the library is missing or cannot be loaded this module raises -- there is no CPU / PyTorch fallback.
 """
 import ctypes as C
-import os
 
 from . import _binding
-from ._binding import AtacomError  # noqa: F401
+from ._binding import AtacomError, OK, E_INVALID, E_HIP, E_UNSUPPORTED  # noqa: F401
 from ._lib import AtacomMlp
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('ATACOM_POINT_POLICY_LIB') or os.path.join(HERE, 'libatacom_point_policy.so')
-
-OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
 
 _vp, _i32, _int, _mlp = C.c_void_p, C.c_int32, C.c_int, C.POINTER(AtacomMlp)
 # {symbol: (restype, argtypes)}: every function of include/atacom_point_policy_hip.h
@@ -25,11 +19,4 @@ SIGNATURES = {
     'atacom_point_policy_rollout_packed': (_int, [_vp, _i32, _vp, _mlp, _vp, _vp, _vp, _i32, _vp]),
 }
 EXPORTS = list(SIGNATURES)
-
-
-def load():
-    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    return _binding.load(LIB_PATH, 'libatacom_point_policy.so', SIGNATURES)
-
-
-check = _binding.checker(load, 'atacom_point_policy_last_error')
+LIB_PATH, load, check = _binding.library('point_policy', SIGNATURES)

@@ -4,15 +4,9 @@ its checkpoint.  It works on the handles of libatacom_point.so (_lib_point).  No
 Like _lib.py: if the library is missing or cannot be loaded this module raises -- there is no CPU / PyTorch fallback.
 """
 import ctypes as C
-import os
 
 from . import _binding
-from ._binding import AtacomError  # noqa: F401
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('ATACOM_POINT_VEC_LIB') or os.path.join(HERE, 'libatacom_point_vec.so')
-
-OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
+from ._binding import AtacomError, OK, E_INVALID, E_HIP, E_UNSUPPORTED  # noqa: F401
 
 _vp, _i32, _i64, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_int
 # {symbol: (restype, argtypes)}: every function of include/atacom_point_vec_hip.h
@@ -26,11 +20,4 @@ SIGNATURES = {
     'atacom_point_vec_snapshot_restore': (_int, [_vp, _vp, _vp]),
 }
 EXPORTS = list(SIGNATURES)
-
-
-def load():
-    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    return _binding.load(LIB_PATH, 'libatacom_point_vec.so', SIGNATURES)
-
-
-check = _binding.checker(load, 'atacom_point_vec_last_error')
+LIB_PATH, load, check = _binding.library('point_vec', SIGNATURES)

@@ -4,16 +4,10 @@ a finished collection.  The library has no handle; a call is one argument struct
 Like _lib.py: if the library is missing or cannot be loaded this module raises -- there is no CPU / PyTorch fallback.
 """
 import ctypes as C
-import os
 
 from . import _binding
-from ._binding import AtacomError  # noqa: F401
+from ._binding import AtacomError, OK, E_INVALID, E_HIP, E_UNSUPPORTED, F32, F64, new_args  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('ATACOM_RETURNS_LIB') or os.path.join(HERE, 'libatacom_returns.so')
-
-OK, E_INVALID, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3
-F32, F64 = 0, 1
 FLAG_U8, FLAG_VALUE = 0, 1
 
 
@@ -47,13 +41,6 @@ class EpisodesArgs(C.Structure):
                 ('reward', View), ('last', View), ('d_workspace', C.c_void_p), ('d_result', C.c_void_p), ('stream', C.c_void_p)]
 
 
-def new_args(cls):
-    """A zeroed argument struct with its struct_size filled in."""
-    a = cls()
-    a.struct_size = C.sizeof(cls)
-    return a
-
-
 _int = C.c_int
 # {symbol: (restype, argtypes)}: every function of include/atacom_returns_hip.h
 SIGNATURES = {
@@ -64,11 +51,4 @@ SIGNATURES = {
     'atacom_returns_episodes': (_int, [C.POINTER(EpisodesArgs)]),
 }
 EXPORTS = list(SIGNATURES)
-
-
-def load():
-    """Load (once) and return the shared library with argtypes set.  Raises if it is not built."""
-    return _binding.load(LIB_PATH, 'libatacom_returns.so', SIGNATURES)
-
-
-check = _binding.checker(load, 'atacom_returns_last_error')
+LIB_PATH, load, check = _binding.library('returns', SIGNATURES)

@@ -2,18 +2,16 @@
 
     python -m rl_on_manifold_amd.build [--force]
 
-TARGETS below describes each library: libatacom_hip.so (the air-hockey and circle tasks), libatacom_point.so (the
+TARGETS below describes each of the seven libraries: libatacom_hip.so (the air-hockey and circle tasks), libatacom_point.so (the
 collision-avoidance task), libatacom_point_policy.so (its rollout with the actor network in the kernel),
 libatacom_point_compact.so (that rollout in the compact record format), libatacom_point_vec.so (the task's masked step and
-checkpoint) and libatacom_returns.so (advantages and episode returns of a finished collection); MORE_TARGETS adds
-libatacom_evaluate.so (critic and actor networks over the rows of a finished collection).  A library is one translation
-unit per group of kernels (they compile in parallel) plus its C-ABI host file, linked into rl_on_manifold_amd/.  The .so files
-are git-ignored.
+checkpoint), libatacom_returns.so (advantages and episode returns of a finished collection) and libatacom_evaluate.so (critic
+and actor networks over the rows of a finished collection).  A library is one translation unit per group of kernels (they compile
+in parallel) plus its C-ABI host file, linked into rl_on_manifold_amd/.  The .so files are git-ignored.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
 than it.  The includes are read from the files themselves (sources()), so there is no list of headers to keep by hand.
 """
-import functools
 import os
 import re
 import subprocess
@@ -21,10 +19,9 @@ import sys
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from ._binding import HERE, naming
+
 CSRC = os.path.join(HERE, 'csrc')
-CSRC_RETURNS = os.path.join(HERE, 'csrc_returns')
-CSRC_EVALUATE = os.path.join(HERE, 'csrc_evaluate')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function'] + \
@@ -43,56 +40,41 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
               'atacom_returns.hip': ['-ffp-contract=off']}
 
-# One description per library: where it is written, the directory of its units, the units, and `tuning`: whether it takes the
-# ATACOM_ONLY_UNITS / kept-object path below.  A new library is a new entry here.
+# One row per library, keyed by its name: the units it compiles and `tuning`, whether it takes the ATACOM_ONLY_UNITS /
+# kept-object path below.  Everything else follows from the key (_binding.naming()).  A new library is a new row here, a
+# binding module with its signatures and structs, and its sources.
 Target = namedtuple('Target', 'lib dir units tuning')
 
 
-def _lib_out(env, name):
-    return os.environ.get(env) or os.path.join(HERE, name)
+def _target(key, units, tuning):
+    n = naming(key)
+    return Target(os.environ.get(n.env + '_OUT') or os.path.join(HERE, n.file), CSRC, units, tuning)
 
 
-TARGETS = {
-    'hip': Target(_lib_out('ATACOM_LIB_OUT', 'libatacom_hip.so'), CSRC, UNITS, True),
+TARGETS = {key: _target(key, *row) for key, row in {
+    'hip': (UNITS, True),
     # The collision-avoidance task (PointReachAtacom) is a library of its own (include/atacom_point_hip.h): its kernels stay
     # out of the main library's census and it shares only headers (the solver of atacom_linalg.h, the host scaffolding of
     # atacom_capi_common.h) with it.
-    'point': Target(_lib_out('ATACOM_POINT_LIB_OUT', 'libatacom_point.so'), CSRC, ['atacom_point.hip', 'atacom_point_capi.cpp'], False),
-    # The task's rollout with the actor network evaluated in the kernel is a third library (include/atacom_point_policy_hip.h):
-    # it borrows the handles of libatacom_point.so (csrc/atacom_point_handle.h) and keeps the kernel census of the other
-    # two as it is.
-    'point_policy': Target(_lib_out('ATACOM_POINT_POLICY_LIB_OUT', 'libatacom_point_policy.so'), CSRC,
-                           ['atacom_point_policy.hip', 'atacom_point_policy_capi.cpp'], False),
-    # The task's rollout in the compact record format is a fourth library (include/atacom_point_compact_hip.h): it borrows the
-    # handles of libatacom_point.so and the network, LDS layout and argument checks of libatacom_point_policy.so, and keeps
-    # the kernel census of the other three as it is.
-    'point_compact': Target(_lib_out('ATACOM_POINT_COMPACT_LIB_OUT', 'libatacom_point_compact.so'), CSRC,
-                            ['atacom_point_compact.hip', 'atacom_point_compact_capi.cpp'], False),
-    # The task's masked step and checkpoint are a fifth library (include/atacom_point_vec_hip.h): it borrows the handles and the
-    # environment (atacom_point.h) of libatacom_point.so and keeps the kernel census of the other four as it is.
-    'point_vec': Target(_lib_out('ATACOM_POINT_VEC_LIB_OUT', 'libatacom_point_vec.so'), CSRC,
-                        ['atacom_point_vec.hip', 'atacom_point_vec_capi.cpp'], False),
-    # The post-processing of a collection (include/atacom_returns_hip.h) is a sixth library that belongs to no environment: it
-    # shares one header with the others, the host scaffolding of csrc/atacom_capi_common.h.
-    'returns': Target(_lib_out('ATACOM_RETURNS_LIB_OUT', 'libatacom_returns.so'), CSRC_RETURNS,
-                      ['atacom_returns.hip', 'atacom_returns_capi.cpp'], False),
-}
+    'point': (['atacom_point.hip', 'atacom_point_capi.cpp'], False),
+    # The task's rollout with the actor network evaluated in the kernel (include/atacom_point_policy_hip.h): it borrows the
+    # handles of libatacom_point.so (atacom_point_handle.h) and keeps the kernel census of the other two as it is.
+    'point_policy': (['atacom_point_policy.hip', 'atacom_point_policy_capi.cpp'], False),
+    # The task's rollout in the compact record format (include/atacom_point_compact_hip.h): it borrows the handles of
+    # libatacom_point.so and the network, LDS layout and argument checks of libatacom_point_policy.so.
+    'point_compact': (['atacom_point_compact.hip', 'atacom_point_compact_capi.cpp'], False),
+    # The task's masked step and checkpoint (include/atacom_point_vec_hip.h): it borrows the handles and the environment
+    # (atacom_point.h) of libatacom_point.so.
+    'point_vec': (['atacom_point_vec.hip', 'atacom_point_vec_capi.cpp'], False),
+    # The post-processing of a collection (include/atacom_returns_hip.h) belongs to no environment: it shares one header with
+    # the others, the host scaffolding of atacom_capi_common.h.
+    'returns': (['atacom_returns.hip', 'atacom_returns_capi.cpp'], False),
+    # The network evaluation of a collection (include/atacom_evaluate_hip.h) belongs to no environment either: it borrows the
+    # network of atacom_policy.h, the description of one (atacom_mlp_host.h) and the host scaffolding by #include, so the
+    # kernel census of the other six stays as it is.
+    'evaluate': (['atacom_evaluate.hip', 'atacom_evaluate_capi.cpp'], False),
+}.items()}
 LIB = TARGETS['hip'].lib
-
-# Libraries added since tests/test_build_table.py pinned TARGETS to the six above, in the same Target type; build(), stale() and
-# build_all() consult this table after TARGETS.  The two tables fold into one when that test may next be edited.
-MORE_TARGETS = {
-    # The network evaluation of a collection (include/atacom_evaluate_hip.h) is a seventh library that belongs to no
-    # environment: its units live in csrc_evaluate/ alone, and it borrows the network of csrc/atacom_policy.h, the description
-    # of one (csrc/atacom_mlp_host.h) and the host scaffolding by #include, so the kernel census of the other six stays as it is.
-    'evaluate': Target(_lib_out('ATACOM_EVALUATE_LIB_OUT', 'libatacom_evaluate.so'), CSRC_EVALUATE,
-                       ['atacom_evaluate.hip', 'atacom_evaluate_capi.cpp'], False),
-}
-
-
-def describe(name):
-    """The description of library `name`, from TARGETS or MORE_TARGETS."""
-    return TARGETS[name] if name in TARGETS else MORE_TARGETS[name]
 
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
 
@@ -116,7 +98,7 @@ def sources(target):
 
 
 def stale(name):
-    tg = describe(name)
+    tg = TARGETS[name]
     if not os.path.exists(tg.lib):
         return True
     t = os.path.getmtime(tg.lib)
@@ -160,9 +142,9 @@ def _hipcc_version():
 
 
 def build(name='hip', force=False, verbose=True):
-    """Build the library `name` of TARGETS or MORE_TARGETS if it is stale (or `force`) and return its path.  The main library is fourteen units
+    """Build the library `name` of TARGETS if it is stale (or `force`) and return its path.  The main library is fourteen units
     and a few minutes, the policy and compact rollouts about a minute each, the others a few seconds."""
-    target = describe(name)
+    target = TARGETS[name]
     if not force and not stale(name):
         return target.lib
     if name == 'hip':
@@ -186,17 +168,8 @@ def build(name='hip', force=False, verbose=True):
 
 
 def build_all(force=False, verbose=True):
-    """Every library of TARGETS and then of MORE_TARGETS, in their order; their paths."""
-    return [build(name, force, verbose) for name in list(TARGETS) + list(MORE_TARGETS)]
-
-
-# Deprecated spellings of build(name) from before the table had every library.  Nothing in this tree calls them; they stay for
-# one release so that callers written against the previous one still work, and go after it.  A new library gets none.
-build_point = functools.partial(build, 'point')
-build_point_policy = functools.partial(build, 'point_policy')
-build_point_compact = functools.partial(build, 'point_compact')
-build_point_vec = functools.partial(build, 'point_vec')
-build_returns = functools.partial(build, 'returns')
+    """Every library of TARGETS, in its order; their paths."""
+    return [build(name, force, verbose) for name in TARGETS]
 
 
 if __name__ == '__main__':

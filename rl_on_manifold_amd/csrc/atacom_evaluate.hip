@@ -13,7 +13,7 @@
 // every lane reaches every MFMA, DPP move and wave-level LDS exchange (rows past the end are computed from zeros and not
 // stored).  Registers and LDS only: no scratch in the float kernels, no atomics, plain vector stores.
 #include "atacom_evaluate.h"
-#include "../csrc/atacom_policy.h"
+#include "atacom_policy.h"
 
 namespace atacom_evaluate {
 

@@ -7,8 +7,8 @@
 
 #include "atacom_evaluate.h"
 #define ATACOM_CAPI_E_HIP ATACOM_EVALUATE_E_HIP
-#include "../csrc/atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
-#include "../csrc/atacom_mlp_host.h"         // mlp_abi_copy
+#include "atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
+#include "atacom_mlp_host.h"         // mlp_abi_copy
 
 namespace {
 

@@ -6,7 +6,7 @@
 
 #include "atacom_returns.h"
 #define ATACOM_CAPI_E_HIP ATACOM_RETURNS_E_HIP
-#include "../csrc/atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
+#include "atacom_capi_common.h"      // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 
 namespace {
 

@@ -1,11 +1,10 @@
 """CPU-only checks of libatacom_evaluate.so, the network evaluation of a collection: the header is plain C11, the declared symbols
 are exactly the exported ones and the ctypes table, every argument rule is enforced without a GPU and with a message, the kernel
 census is the sixteen instantiations, the float32 kernels use no scratch and every kernel the documented LDS, the exec-mask audit
-finds nothing, the Python signatures are the documented ones and the build table of the six earlier libraries is untouched.  No
+finds nothing and the Python signatures are the documented ones (its row of the build table: tests/test_build_table.py).  No
 compute call is made (no GPU here)."""
 import ctypes
 import inspect
-import os
 import subprocess
 
 import pytest
@@ -253,35 +252,3 @@ def test_python_surface():
     assert pkg.evaluate_mlp is evaluate.evaluate_mlp and pkg.values_from_compact is evaluate.values_from_compact
     assert params(pkg.MlpPolicy.as_struct_on) == pos('self', 'device', 'dtype')
     assert params(pkg.MlpPolicy.as_struct) == pos('self', 'env')
-
-
-def test_the_six_targets_are_untouched_and_build_all_returns_seven(monkeypatch):
-    from rl_on_manifold_amd import build
-    assert list(build.TARGETS) == ['hip', 'point', 'point_policy', 'point_compact', 'point_vec', 'returns']
-    assert list(build.MORE_TARGETS) == ['evaluate']
-    t = build.MORE_TARGETS['evaluate']
-    assert isinstance(t, build.Target) and t.dir == build.CSRC_EVALUATE == os.path.join(build.HERE, 'csrc_evaluate')
-    assert os.path.basename(t.lib) == 'libatacom_evaluate.so' or os.environ.get('ATACOM_EVALUATE_LIB_OUT')
-    assert t.units == ['atacom_evaluate.hip', 'atacom_evaluate_capi.cpp'] and not t.tuning
-    assert sorted(f for f in os.listdir(t.dir) if f.endswith(('.h', '.hip', '.cpp'))) == \
-        ['atacom_evaluate.h', 'atacom_evaluate.hip', 'atacom_evaluate_capi.cpp']
-    assert build.describe('evaluate') is t and build.describe('returns') is build.TARGETS['returns']
-    # it borrows by #include: the network, its host description and the scaffolding -- and lends nothing
-    src = {os.path.basename(p) for p in build.sources(t)}
-    own = {'atacom_evaluate.h', 'atacom_evaluate.hip', 'atacom_evaluate_capi.cpp', 'atacom_evaluate_hip.h'}
-    assert own | {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h', 'atacom_hip.h'} == src
-    for other in build.TARGETS.values():
-        assert not own & {os.path.basename(p) for p in build.sources(other)}
-    # stale() follows the same rule for it
-    touched = abi.fake_mtimes(monkeypatch, build)
-    real = build.os.path.exists
-    monkeypatch.setattr(build.os.path, 'exists', lambda p: p == t.lib or real(p))
-    assert not build.stale('evaluate')
-    for name, want in (('atacom_policy.h', True), ('atacom_evaluate.hip', True), ('atacom_returns.hip', False), ('atacom_point.h', False)):
-        touched[:] = [name]
-        assert build.stale('evaluate') == want, name
-    monkeypatch.undo()
-    # build_all: the six, then the seventh, each an existing file (a library that is up to date is not compiled again)
-    libs = build.build_all(verbose=False)
-    assert libs == [x.lib for x in build.TARGETS.values()] + [t.lib] and len(libs) == 7
-    assert all(os.path.exists(p) for p in libs)

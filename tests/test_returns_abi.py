@@ -161,7 +161,7 @@ def test_the_scan_kernels_have_no_barrier_and_only_the_explicit_fused_operations
     bodies = abi.function_bodies(returns_lib, tmp_path)
     assert len({elf for elf, _, _ in bodies}) == 1
     # the depth this build was compiled with: the header's default unless ATACOM_HIPCC_FLAGS overrides it
-    header = open(os.path.join(abi.ROOT, 'rl_on_manifold_amd', 'csrc_returns', 'atacom_returns.h')).read()
+    header = open(os.path.join(abi.ROOT, 'rl_on_manifold_amd', 'csrc', 'atacom_returns.h')).read()
     override = re.search(r'-DATACOM_RETURNS_DEPTH=(\d+)', os.environ.get('ATACOM_HIPCC_FLAGS', ''))
     depth = int((override or re.search(r'define ATACOM_RETURNS_DEPTH (\d+)', header)).group(1))
     seen = 0
