@@ -5,15 +5,15 @@ Not part of the hot path: the reference trains with MushroomRL's PPO (examples/p
 examples/iiwa_air_hockey_exp.py:137-170), which is not installed here.  This script shows the same loop shape on the
 engine: collection = ONE kernel launch per iteration (policy MLP + exploration noise + ATACOM env step fused, written as packed
 records: `rollout_packed`), the critic on obs and next_obs and the log-probability of the drawn actions = three more, read from
-the records in place (`values_from_records`, `log_prob_from_records`), advantages = one more (`gae_from_records`), policy /
-value update = plain torch autograd on the GPU.
+the records in place (`values_from_records`, `log_prob_from_records`), advantages = one more (`gae_from_records`), and the
+gradients of a minibatch = one launch per network, gathered from the records through the minibatch's row numbers
+(`policy_gradient_from_records`, `value_gradient_from_records`); the optimiser is torch's Adam, which takes them as .grad.
 Network = the reference's PPONetwork (examples/network.py:8-36: Linear-ReLU-Linear-ReLU-Linear, 64 units), Gaussian policy with
 state-independent std.
 
     python examples/ppo_air_hockey.py --env planar --iters 60
 """
 import argparse
-import math
 import os
 import sys
 import time
@@ -23,7 +23,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere in the checkout
 from rl_on_manifold_amd import (BatchedAtacomEnv, MlpPolicy, RecordLayout, gae_from_records, log_prob_from_records,
-                                values_from_records)
+                                policy_gradient_from_records, value_gradient_from_records, values_from_records)
 
 
 class Net(nn.Module):                      # same layer names as the reference's PPONetwork
@@ -61,15 +61,17 @@ def main():
     log_std = torch.full((k,), -0.7, device=dev, requires_grad=True)          # std_0 = 0.5
     opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
     gamma, lam, clip, epochs, mb = 0.99, 0.95, 0.2, 4, 16384
-    norm = lambda o: (o - shift) * scale                                     # noqa: E731
     lay = RecordLayout([B], D, k)
-    log_norm = 0.5 * k * math.log(2.0 * math.pi)                              # the Gaussian's constant, as log_prob_from_records has it
+    # The networks as the kernels see them, made once: the weights are the modules' own storage, so Adam's in-place steps are
+    # seen by the next launch; std is a tensor of the policy that follows log_std (refreshed in place after every step).
+    std = log_std.detach().exp()
+    pol, cri = MlpPolicy.from_module(actor, std=std), MlpPolicy.from_module(critic)
+    for net in (pol, cri):
+        net.tensors['obs_shift'], net.tensors['obs_scale'] = shift, scale
+    gp = gc = None                                                            # the gradients' buffers, reused by every call
     t_collect = t_fit = 0.0
     for it in range(args.iters):
         t0 = time.perf_counter()
-        pol, cri = MlpPolicy.from_module(actor, std=log_std.detach().exp()), MlpPolicy.from_module(critic)
-        for net in (pol, cri):
-            net.tensors['obs_shift'], net.tensors['obs_scale'] = shift, scale
         noise = torch.randn((T, B, k), device=dev)
         env.reset()
         rec = env.rollout_packed(policy=pol, n_steps=T, noise=noise)          # ONE launch: T steps of B envs, [T, B, 2 D + k + 3]
@@ -84,21 +86,20 @@ def main():
         ret, adv, _ = gae_from_records(lay, rec, v, nv, gamma, lam, normalize=True)
         logp_old = log_prob_from_records(lay, rec, pol)
         d = lay.unpack(rec)
-        obs, act, rew, last = norm(d['obs']), d['action'], d['reward'], d['last']
-        flat = lambda x: x.reshape(T * B, *x.shape[2:])                       # noqa: E731
-        fo, fa, fadv, fret, flp = flat(obs), flat(act), flat(adv), flat(ret), flat(logp_old)
+        rew, last = d['reward'], d['last']
         for _ in range(epochs):
             perm = torch.randperm(T * B, device=dev)
             for i in range(0, T * B, mb):
-                idx = perm[i:i + mb]
-                mu = actor(fo[idx])
-                logp = (-0.5 * ((fa[idx] - mu) / log_std.exp()) ** 2 - log_std).sum(-1) - log_norm
-                ratio = (logp - flp[idx]).exp()
-                pl = -torch.min(ratio * fadv[idx], ratio.clamp(1 - clip, 1 + clip) * fadv[idx]).mean()
-                vl = (critic(fo[idx]).squeeze(-1) - fret[idx]).pow(2).mean()
-                opt.zero_grad()
-                (pl + 0.5 * vl).backward()
+                idx = perm[i:i + mb]                                          # row numbers into the flat [T * B] records
+                # the gradients of  -min(ratio adv, clamp(ratio) adv).mean()  and  (critic(obs) - ret).pow(2).mean()  over the rows
+                # idx names: forward and backward pass of each network in one launch, obs and action read from the records
+                gp = policy_gradient_from_records(lay, rec, adv, logp_old, pol, clip=clip, idx=idx, out=gp)
+                gc = value_gradient_from_records(lay, rec, ret, cri, idx=idx, out=gc)
+                gc.flat.mul_(0.5)                                             # the loss is  policy + 0.5 value
+                gp.to_module(actor, log_std)
+                gc.to_module(critic)
                 opt.step()
+                std.copy_(log_std.detach().exp())
         torch.cuda.synchronize()
         t_fit += time.perf_counter() - t0
         ep_ret = rew.sum(0).mean().item() if not last[:-1].any() else (rew.sum() / last.sum().clamp_min(1)).item()

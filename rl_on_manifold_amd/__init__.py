@@ -28,6 +28,9 @@ def __getattr__(name):
                 'evaluate_rows'):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ('value_gradient', 'policy_gradient', 'value_gradient_from_records', 'policy_gradient_from_records', 'Gradients'):
+        from . import fit
+        return getattr(fit, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

@@ -9,6 +9,12 @@ checkpoint), libatacom_returns.so (advantages and episode returns of a finished 
 and actor networks over the rows of a finished collection).  A library is one translation unit per group of kernels (they compile
 in parallel) plus its C-ABI host file, linked into rl_on_manifold_amd/.  The .so files are git-ignored.
 
+EXTENSIONS holds what is built beside that table, in rows of the same kind: libatacom_fit.so (the gradients of the PPO policy and
+value losses, include/atacom_fit_hip.h), the eighth library.  It is not a row of TARGETS because the seven, their units, the
+files directly inside csrc/ and their kernel census are pinned by the tests that guard them against accidental growth; a
+library that only borrows headers by #include lives in a sub-directory of csrc/ (csrc/fit/) and in this second table, and
+build(), stale() and sources() take its key like any other.  build_all() builds the seven, build_extensions() the rest.
+
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
 than it.  The includes are read from the files themselves (sources()), so there is no list of headers to keep by hand.
 """
@@ -46,9 +52,9 @@ UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterat
 Target = namedtuple('Target', 'lib dir units tuning')
 
 
-def _target(key, units, tuning):
+def _target(key, units, tuning, sub=''):
     n = naming(key)
-    return Target(os.environ.get(n.env + '_OUT') or os.path.join(HERE, n.file), CSRC, units, tuning)
+    return Target(os.environ.get(n.env + '_OUT') or os.path.join(HERE, n.file), os.path.join(CSRC, sub) if sub else CSRC, units, tuning)
 
 
 TARGETS = {key: _target(key, *row) for key, row in {
@@ -76,6 +82,17 @@ TARGETS = {key: _target(key, *row) for key, row in {
 }.items()}
 LIB = TARGETS['hip'].lib
 
+# Libraries beside the table (the module docstring says why): same rows, sources in a sub-directory of csrc/.
+# The gradients of an on-policy update (include/atacom_fit_hip.h): it borrows the network of atacom_policy.h, its host
+# description and the host scaffolding by `#include "../..."`, and adds no kernel or symbol to the seven.
+EXTENSIONS = {
+    'fit': _target('fit', ['atacom_fit.hip', 'atacom_fit_capi.cpp'], False, sub='fit'),
+}
+
+
+def _row(name):
+    return TARGETS[name] if name in TARGETS else EXTENSIONS[name]
+
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
 
 
@@ -83,7 +100,9 @@ def sources(target):
     """What a library is rebuilt for: its units and every file they reach through `#include "..."` lines.  The scan is textual
     (an include under a false #if, or at the start of a line of a /* */ comment, counts: that errs on the side of rebuilding,
     and such a line must name a file that exists), a name is resolved relative to the including file, and <...> includes are
-    not followed."""
+    not followed.  `target` is a row or the key of one."""
+    if isinstance(target, str):
+        target = _row(target)
     out = [os.path.join(target.dir, u) for u in target.units]
     for path in out:                                 # grows while it is walked
         with open(path, encoding='utf-8', errors='replace') as fh:
@@ -98,7 +117,7 @@ def sources(target):
 
 
 def stale(name):
-    tg = TARGETS[name]
+    tg = _row(name)
     if not os.path.exists(tg.lib):
         return True
     t = os.path.getmtime(tg.lib)
@@ -142,9 +161,9 @@ def _hipcc_version():
 
 
 def build(name='hip', force=False, verbose=True):
-    """Build the library `name` of TARGETS if it is stale (or `force`) and return its path.  The main library is fourteen units
+    """Build the library `name` of TARGETS or EXTENSIONS if it is stale (or `force`) and return its path.  The main library is fourteen units
     and a few minutes, the policy and compact rollouts about a minute each, the others a few seconds."""
-    target = TARGETS[name]
+    target = _row(name)
     if not force and not stale(name):
         return target.lib
     if name == 'hip':
@@ -172,5 +191,10 @@ def build_all(force=False, verbose=True):
     return [build(name, force, verbose) for name in TARGETS]
 
 
+def build_extensions(force=False, verbose=True):
+    """Every library of EXTENSIONS, in its order; their paths."""
+    return [build(name, force, verbose) for name in EXTENSIONS]
+
+
 if __name__ == '__main__':
-    print('\n'.join(build_all(force='--force' in sys.argv)))
+    print('\n'.join(build_all(force='--force' in sys.argv) + build_extensions(force='--force' in sys.argv)))
