@@ -632,6 +632,32 @@ __device__ __forceinline__ void iiwa_prepare_group(const Params<T>& P, const T (
     }
 }
 
+// ------------------------------------------------------------------ parameters read where they are used
+// Params is a by-value kernel argument of ~100 dwords and the compiler loads nearly all of it at kernel entry -- the puck,
+// reward, observation and reset constants included, which are first read AFTER the sub-step loop.  The 8-lane float32
+// kernels have no scalar registers left for them across the solver: they were carried in the lanes of a vector register
+// (38 v_writelane + 86 v_readlane in the single-step kernel, profiles/step_spill_traffic.md).  With PARAMS_REREAD the code
+// behind the loop reads its parameters from the kernel-argument segment again, through a pointer the optimiser cannot see
+// through (the empty asm), so nothing is held across the loop.  The copy is dissolved into the scalar loads of the fields
+// that are read: no struct in scratch.  Only right where Params<T> is the FIRST kernel argument (k_step, k_rollout,
+// k_rollout_mlp: the kernels that call env_step).
+// The switch is a template argument of env_step that k_step alone sets, for the headline instantiation alone: 9 484 -> 9 331
+// executed vector instructions per wave, 22.53 -> 21.99 us per step at 8192 environments.  The T-step kernels of the same
+// family were built with it and keep their text: their step loop holds the kernel's pointers and the solver's copies across
+// everything, they still spill with it (110 / 160 scalar registers) and k_rollout gained 0.7 % (step_spill_traffic.md,
+// section 8).  Every other instantiation keeps its text and its machine code.
+template <typename T, typename E, int LN, bool HOLD, bool DYN, int CHART, bool NOISE>
+constexpr bool PARAMS_REREAD = (LN == 8) && std::is_same<T, float>::value && std::is_same<E, Iiwa>::value && HOLD && !DYN &&
+                               CHART == 0 && !NOISE;
+template <typename T>
+__device__ __forceinline__ void params_reread(Params<T>& Q) {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();           // a pointer into the constant address space: scalar loads
+    asm volatile("" : "+s"(p));
+    // (through a pointer to Params: the copy then knows its alignment -- from a void pointer the fields arrive by VECTOR
+    // loads, in vector registers)
+    __builtin_memcpy(&Q, (const __attribute__((address_space(4))) Params<T>*)p, sizeof(Q));
+}
+
 // ------------------------------------------------------------------ one env step (A1, A2, A13-A15)
 // LANES = 1: one environment per lane (atacom_linalg.h).  LANES = 4: one environment per DPP quad -- the
 // null-space solve is column-split over the quad (atacom_quad.h), everything else is computed redundantly
@@ -648,7 +674,7 @@ __device__ __forceinline__ void iiwa_prepare_group(const Params<T>& P, const T (
 // test_policy_rollout_in_rigid_body_mode).  A compiler defect that depends on register pressure, not on this source: every
 // kernel of the built library is audited for the pattern (tests/test_kernel_resources.py, profiles/tools/exec_restore_audit.py).
 template <typename T, typename E, int LANES, bool HOLD, bool DYN = false, bool HOIST_G0 = true, int CHART = 0,
-          int THREADS = BLOCK<LANES>, bool PARKDYN = false, typename Ref>
+          int THREADS = BLOCK<LANES>, bool PARKDYN = false, bool REREAD = false, typename Ref>
 __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st, const T (&act)[E::NK],
                                          StepOut<T>& out, const int lq, const Ref& ref) {
     using L = Planes<E>;
@@ -994,6 +1020,10 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
         }
     }
     ATACOM_MARK("POST_fk");
+    [[maybe_unused]] Params<T> Pre;
+    const Params<T>* pp = &P;
+    if constexpr (REREAD) { params_reread(Pre); pp = &Pre; }
+    const Params<T>& Q = *pp;   // what follows the sub-step loop reads its parameters here
     if (E::ID == 0) {
         const T dx = T(1) - st.q[0];
         out.reward = num<T>::exp(-num<T>::sqrt(num<T>::fma(dx, dx, st.q[1] * st.q[1])));   // circle_base.py:65
@@ -1007,22 +1037,22 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
             group_sincos6<T, LANES>(st.q, oh, sn, cs);
             IiwaKin<T> kin;
             iiwa_chain(sn, cs, kin);
-            iiwa_fun_from_kin(P, kin, st.q, fun, mxy);
+            iiwa_fun_from_kin(Q, kin, st.q, fun, mxy);
         } else {
-            constraint_fun(E{}, P, st.q, fun, mxy);
+            constraint_fun(E{}, Q, st.q, fun, mxy);
         }
         // ---- puck (row N1): the arm is kinematic w.r.t. the puck, so the puck's sub-steps run after the arm's,
         // against a mallet moving uniformly from (m0x, m0y) to mxy over the env step.  Frictionless disc,
         // impulse + push-out at the mallet, elastic rims, open goal mouths (env_hitting.py:44-45).
         ATACOM_MARK("POST_puck");
         {
-            const T inv_n = num<T>::rcp((T)P.substeps);
-            const T ux = (mxy[0] - m0x) * inv_n / P.dt, uy = (mxy[1] - m0y) * inv_n / P.dt;
-            const T R = P.puck_r + P.mallet_r;
-            const T ylim = P.table_hy - P.puck_r, xlim = P.table_hx - P.puck_r;
+            const T inv_n = num<T>::rcp((T)Q.substeps);
+            const T ux = (mxy[0] - m0x) * inv_n / Q.dt, uy = (mxy[1] - m0y) * inv_n / Q.dt;
+            const T R = Q.puck_r + Q.mallet_r;
+            const T ylim = Q.table_hy - Q.puck_r, xlim = Q.table_hx - Q.puck_r;
             // domain randomisation (NOISE kernels only)
-            const bool delay = E::PUCK && Ref::noise && (P.noise & NOISE_DELAY) != 0;
-            const bool kick = E::PUCK && Ref::noise && (P.noise & NOISE_ENV) != 0;
+            const bool delay = E::PUCK && Ref::noise && (Q.noise & NOISE_DELAY) != 0;
+            const bool kick = E::PUCK && Ref::noise && (Q.noise & NOISE_ENV) != 0;
             T fvp[3] = {T(0), T(0), T(0)};
             int ep_run = 0;
             if constexpr (E::PUCK && Ref::noise) {
@@ -1033,7 +1063,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                 if (kick) ep_run = pli(ref.ip, L::I_EP, ref.b) - 1;
             }
 #pragma unroll 1
-            for (int k = 0; k < P.substeps; ++k) {
+            for (int k = 0; k < Q.substeps; ++k) {
                 const T fr = (T)(k + 1) * inv_n;
                 const T mx = num<T>::fma(mxy[0] - m0x, fr, m0x), my = num<T>::fma(mxy[1] - m0y, fr, m0y);
                 if constexpr (E::PUCK && Ref::noise) {
@@ -1042,16 +1072,16 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                         for (int i = 0; i < 3; ++i) fvp[i] = num<T>::fma(T(0.5), st.puck[3 + i], T(0.5) * fvp[i]);
                     }
                     if (kick) {                  // _simulation_pre_step, env_base.py:176-180: force 0.0005 [randn, randn, 0]
-                        const int n_idx = 3 + 2 * P.substeps;
+                        const int n_idx = 3 + 2 * Q.substeps;
 #pragma unroll
                         for (int c = 0; c < 2; ++c)
-                            st.puck[3 + c] = num<T>::fma(P.env_noise_dv,
-                                                         device_normal<T>(P.seed, ref.b, ep_run, st.t, 3 + 2 * k + c, n_idx),
+                            st.puck[3 + c] = num<T>::fma(Q.env_noise_dv,
+                                                         device_normal<T>(Q.seed, ref.b, ep_run, st.t, 3 + 2 * k + c, n_idx),
                                                          st.puck[3 + c]);
                     }
                 }
 #pragma unroll
-                for (int i = 0; i < 3; ++i) st.puck[i] = num<T>::fma(st.puck[3 + i], P.dt, st.puck[i]);
+                for (int i = 0; i < 3; ++i) st.puck[i] = num<T>::fma(st.puck[3 + i], Q.dt, st.puck[i]);
                 const T dxm = st.puck[0] - mx, dym = st.puck[1] - my;
                 const T dist = num<T>::sqrt(num<T>::fma(dxm, dxm, dym * dym));
                 const bool hit = dist < R;
@@ -1060,7 +1090,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                 const T nx = pos ? dxm * idist : T(1), ny = pos ? dym * idist : T(0);
                 const T vrel = (st.puck[3] - ux) * nx + (st.puck[4] - uy) * ny;
                 const bool imp = hit && (vrel < T(0));
-                const T jimp = imp ? (T(1) + P.e_mallet) * vrel : T(0);
+                const T jimp = imp ? (T(1) + Q.e_mallet) * vrel : T(0);
                 st.puck[3] = num<T>::fma(-jimp, nx, st.puck[3]);
                 st.puck[4] = num<T>::fma(-jimp, ny, st.puck[4]);
                 st.puck[0] = hit ? num<T>::fma(nx, R, mx) : st.puck[0];
@@ -1070,18 +1100,18 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                     const bool oy = ay > ylim;
                     const T sg = st.puck[1] > T(0) ? T(1) : (st.puck[1] < T(0) ? T(-1) : T(0));
                     st.puck[1] = oy ? sg * (T(2) * ylim - ay) : st.puck[1];
-                    st.puck[4] = (oy && st.puck[4] * sg > T(0)) ? -P.e_rim * st.puck[4] : st.puck[4];
+                    st.puck[4] = (oy && st.puck[4] * sg > T(0)) ? -Q.e_rim * st.puck[4] : st.puck[4];
                 }
                 bool own_rim;   // the puck met the end rim on the agent's side (x < 0) in this sub-step
                 {   // end rims, open in the goal mouth
                     const T ax = num<T>::abs(st.puck[0]);
-                    const bool ox = (ax > xlim) && (num<T>::abs(st.puck[1]) >= P.goal_w);
+                    const bool ox = (ax > xlim) && (num<T>::abs(st.puck[1]) >= Q.goal_w);
                     const T sg = st.puck[0] > T(0) ? T(1) : (st.puck[0] < T(0) ? T(-1) : T(0));
                     own_rim = ox && (sg < T(0));
                     st.puck[0] = ox ? sg * (T(2) * xlim - ax) : st.puck[0];
-                    st.puck[3] = (ox && st.puck[3] * sg > T(0)) ? -P.e_rim * st.puck[3] : st.puck[3];
+                    st.puck[3] = (ox && st.puck[3] * sg > T(0)) ? -Q.e_rim * st.puck[3] : st.puck[3];
                 }
-                if (E::ID == 1 && P.task == 1) {
+                if (E::ID == 1 && Q.task == 1) {
                     // task 'D' (AirHockeyDefend._simulation_post_step [upstream]): has_hit (bit 0) latches on puck / mallet
                     // contact, has_bounce (bit 1) on contact with the end rims of the agent's side
                     st.has_hit |= (hit ? 1 : 0) | (own_rim ? 2 : 0);
@@ -1105,13 +1135,13 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
         ATACOM_MARK("POST_reward");
         // absorbing: env_base.py:182-194 + env_hitting.py:71-78
         const T pv2 = num<T>::fma(st.puck[3], st.puck[3], st.puck[4] * st.puck[4]);
-        bool ab = (num<T>::abs(st.puck[0]) > P.table_hx) || (num<T>::abs(st.puck[1]) > P.table_hy);
-        ab = ab || (num<T>::abs(mxy[0]) - P.table_hx > T(0.02)) || (num<T>::abs(mxy[1]) - P.table_hy > T(0.02));
+        bool ab = (num<T>::abs(st.puck[0]) > Q.table_hx) || (num<T>::abs(st.puck[1]) > Q.table_hy);
+        ab = ab || (num<T>::abs(mxy[0]) - Q.table_hx > T(0.02)) || (num<T>::abs(mxy[1]) - Q.table_hy > T(0.02));
         T r;
-        if (E::ID == 1 && P.task == 1) {
+        if (E::ID == 1 && Q.task == 1) {
             // task 'D': AirHockeyDefend.is_absorbing / .reward [upstream, restated from memory; DESIGN.md section 4]
             ab = ab || ((st.has_hit != 0) && (st.puck[0] > T(0)));             // hit or bounced, and back in the other half
-            const bool conceded = (st.puck[0] + P.table_hx < T(0)) && (num<T>::abs(st.puck[1]) - P.goal_w < T(0));
+            const bool conceded = (st.puck[0] + Q.table_hx < T(0)) && (num<T>::abs(st.puck[1]) - Q.goal_w < T(0));
             const T apy = num<T>::abs(st.puck[1]);
             // after a hit: the puck resting near the line x = -0.6 on the agent's side
             const T r_y = T(3) * num<T>::exp(T(-3) * apy);
@@ -1129,10 +1159,10 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
         } else {
         ab = ab || ((st.has_hit != 0) && (pv2 < T(0.0001)));
         // reward: env_hitting.py:39-69
-        const bool goal = (st.puck[0] - P.table_hx > T(0)) && (num<T>::abs(st.puck[1]) - P.goal_w < T(0));
+        const bool goal = (st.puck[0] - Q.table_hx > T(0)) && (num<T>::abs(st.puck[1]) - Q.goal_w < T(0));
         const T dx = st.puck[0] - mxy[0], dy = st.puck[1] - mxy[1];
         const T dist = num<T>::sqrt(num<T>::fma(dx, dx, dy * dy));
-        const T gx = P.goal_x - st.puck[0], gy = P.goal_y - st.puck[1];
+        const T gx = Q.goal_x - st.puck[0], gy = Q.goal_y - st.puck[1];
         const T gn = num<T>::sqrt(num<T>::fma(gx, gx, gy * gy));
         const T ign = num<T>::rcp(gn), idist = num<T>::rcp(dist);
         T cosang = num<T>::fma(gx * ign, dx * idist, (gy * ign) * (dy * idist));      // (explicit contraction, as below)
@@ -1142,18 +1172,18 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
         st.r_hit = upd ? r_app : st.r_hit;
         r = ab ? (goal ? T(80) : T(0)) : ((st.has_hit != 0) ? num<T>::fma(st.vel_hit_x, T(0.1), T(1) + st.r_hit) : r_app);
         }
-        out.reward = num<T>::fma(-P.action_penalty, num<T>::sqrt(anorm2), r);     // explicit: the same contraction in every kernel
+        out.reward = num<T>::fma(-Q.action_penalty, num<T>::sqrt(anorm2), r);     // explicit: the same contraction in every kernel
         out.absorbing = ab;
         // constraint statistics, atacom.py:201-205
         T cm = num<T>::abs(fun[0]);
         if (NF == 0) cm = fun[0];
 #pragma unroll
         for (int r2 = 1; r2 < NC; ++r2) cm = num<T>::max(cm, (r2 < NF) ? num<T>::abs(fun[r2]) : fun[r2]);
-        T dm = num<T>::abs(st.dq[0]) - P.vel_max[0];
+        T dm = num<T>::abs(st.dq[0]) - Q.vel_max[0];
 #pragma unroll
-        for (int i = 1; i < NQ; ++i) dm = num<T>::max(dm, num<T>::abs(st.dq[i]) - P.vel_max[i]);
+        for (int i = 1; i < NQ; ++i) dm = num<T>::max(dm, num<T>::abs(st.dq[i]) - Q.vel_max[i]);
         if constexpr (E::PUCK && Ref::noise) {
-            if (P.noise & NOISE_DELAY) {
+            if (Q.noise & NOISE_DELAY) {
                 // the observation the step returns advances the low-pass once more (env_single.py:114-119; the puck's part
                 // was stored right after its sub-steps), and _update_constraint_stats gets the wrapper's dq = the observation's (atacom.py:111-114)
 #pragma unroll
@@ -1161,7 +1191,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
                     const T fo = pl<E>(ref.f, L::FV + 3 + i, ref.B, ref.b);
                     const T fn = num<T>::fma(T(0.5), st.dq[i], T(0.5) * fo);
                     if (ref.commit) pl<E>(ref.f, L::FV + 3 + i, ref.B, ref.b) = fn;
-                    const T d = num<T>::abs(fn) - P.vel_max[i];
+                    const T d = num<T>::abs(fn) - Q.vel_max[i];
                     dm = (i == 0) ? d : num<T>::max(dm, d);
                 }
             }
@@ -1170,7 +1200,7 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
         out.log_dq = dm;
     }
     st.t += 1;
-    out.last = out.absorbing || (st.t >= P.horizon);
+    out.last = out.absorbing || (st.t >= Q.horizon);
 }
 
 // ------------------------------------------------------------------ kernels
@@ -1220,24 +1250,47 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_step(const Params<T> P, T* __r
     unsigned long long ts1;
     asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts1) : "v"(st.q[0]) : "memory");
 #endif
-    env_step<T, E, LANES, HOLD, DYN, true, CHART>(P, st, act, out, lq, ref);
+    constexpr bool REREAD = PARAMS_REREAD<T, E, LANES, HOLD, DYN, CHART, NOISE>;
+    env_step<T, E, LANES, HOLD, DYN, true, CHART, BLOCK<LANES>, false, REREAD>(P, st, act, out, lq, ref);
     ATACOM_MARK("STORE");
 #ifdef ATACOM_TIMESTAMPS
     unsigned long long ts2;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts2) : "v"(out.reward) : "memory");
 #endif
     if (lq != 0) return;                       // the four lanes hold identical results; lane 0 writes
-    write_obs<T, E>(P, st, obs + (size_t)b * E::OBS, ref);
-    reward[b] = out.reward;
-    absorbing[b] = out.absorbing ? 1 : 0;
-    if (last) last[b] = out.last ? 1 : 0;
-    pl<E>(f, L::SSUM, B, b) = ssum0 + out.log_avg;
-    pl<E>(f, L::SCMAX, B, b) = num<T>::max(scmax0, out.log_max);
-    pl<E>(f, L::SDQMAX, B, b) = num<T>::max(sdq0, out.log_dq);
-    pli(ip, L::I_CNT, b) = cnt0 + 1;
-    if (P.auto_reset && out.last) reset_env<T, E>(P, ref, st);
-    store_state<T, E>(f, ip, B, b, st);
-    if constexpr (DYN) store_aux<T, E>(f, B, b, st);
+    if constexpr (REREAD) {
+        // The store tail, with its addresses formed anew from the environment's index.  The loads at the top computed the same
+        // twelve 64-bit addresses, and the compiler kept them for the stores -- in accumulation registers across the solver,
+        // 24 copies out and 22 back; formed again they are 14 additions (profiles/step_spill_traffic.md).  The text below
+        // is the tail of every other instantiation with (bs, refs) for (b, ref); theirs stays as it was, so that their
+        // machine code does (a shared form commuted one addition in each of them)
+        int bs = b;
+        asm volatile("" : "+v"(bs));
+        const EnvRef<T, NOISE> refs{f, ip, B, bs, true};
+        write_obs<T, E>(P, st, obs + (size_t)bs * E::OBS, refs);
+        reward[bs] = out.reward;
+        absorbing[bs] = out.absorbing ? 1 : 0;
+        if (last) last[bs] = out.last ? 1 : 0;
+        pl<E>(f, L::SSUM, B, bs) = ssum0 + out.log_avg;
+        pl<E>(f, L::SCMAX, B, bs) = num<T>::max(scmax0, out.log_max);
+        pl<E>(f, L::SDQMAX, B, bs) = num<T>::max(sdq0, out.log_dq);
+        pli(ip, L::I_CNT, bs) = cnt0 + 1;
+        if (P.auto_reset && out.last) reset_env<T, E>(P, refs, st);
+        store_state<T, E>(f, ip, B, bs, st);
+        if constexpr (DYN) store_aux<T, E>(f, B, bs, st);
+    } else {
+        write_obs<T, E>(P, st, obs + (size_t)b * E::OBS, ref);
+        reward[b] = out.reward;
+        absorbing[b] = out.absorbing ? 1 : 0;
+        if (last) last[b] = out.last ? 1 : 0;
+        pl<E>(f, L::SSUM, B, b) = ssum0 + out.log_avg;
+        pl<E>(f, L::SCMAX, B, b) = num<T>::max(scmax0, out.log_max);
+        pl<E>(f, L::SDQMAX, B, b) = num<T>::max(sdq0, out.log_dq);
+        pli(ip, L::I_CNT, b) = cnt0 + 1;
+        if (P.auto_reset && out.last) reset_env<T, E>(P, ref, st);
+        store_state<T, E>(f, ip, B, b, st);
+        if constexpr (DYN) store_aux<T, E>(f, B, b, st);
+    }
 #ifdef ATACOM_TIMESTAMPS
     {   // overwrite the first observation entries with the stamps (low 32 bits, 10 ns ticks); ts3 after the stores landed
         unsigned long long ts3;
