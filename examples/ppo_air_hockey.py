@@ -7,7 +7,10 @@ engine: collection = ONE kernel launch per iteration (policy MLP + exploration n
 records: `rollout_packed`), the critic on obs and next_obs and the log-probability of the drawn actions = three more, read from
 the records in place (`values_from_records`, `log_prob_from_records`), advantages = one more (`gae_from_records`), and the
 gradients of a minibatch = one launch per network, gathered from the records through the minibatch's row numbers
-(`policy_gradient_from_records`, `value_gradient_from_records`); the optimiser is torch's Adam, which takes them as .grad.
+(`policy_gradient_from_records`, `value_gradient_from_records`), and the optimiser step = one more for both networks and log
+std (`Adam`), its state on the device -- so an epoch of minibatches is ONE graph replay (`GraphedUpdate`) with a permutation
+drawn on the device.  `--update torch` runs the loop this replaces -- the same gradient calls, torch's Adam taking them as
+.grad, one Python iteration per minibatch -- for comparison.
 Network = the reference's PPONetwork (examples/network.py:8-36: Linear-ReLU-Linear-ReLU-Linear, 64 units), Gaussian policy with
 state-independent std.
 
@@ -22,8 +25,9 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere in the checkout
-from rl_on_manifold_amd import (BatchedAtacomEnv, MlpPolicy, RecordLayout, gae_from_records, log_prob_from_records,
-                                policy_gradient_from_records, value_gradient_from_records, values_from_records)
+from rl_on_manifold_amd import (Adam, BatchedAtacomEnv, GraphedUpdate, MlpPolicy, RecordLayout, gae_from_records,
+                                log_prob_from_records, policy_gradient_from_records, value_gradient_from_records,
+                                values_from_records)
 
 
 class Net(nn.Module):                      # same layer names as the reference's PPONetwork
@@ -46,6 +50,8 @@ def main():
     ap.add_argument('--horizon', type=int, default=120)
     ap.add_argument('--lr', type=float, default=3e-4)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--update', default='graph', choices=['graph', 'torch'],
+                    help="'graph': the device Adam, an epoch replayed as one graph; 'torch': torch.optim.Adam in a Python loop")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     dev = torch.device('cuda:0')
@@ -59,7 +65,6 @@ def main():
     scale[3:6] = 0.2
     actor, critic = Net(D, k).to(dev), Net(D, 1).to(dev)
     log_std = torch.full((k,), -0.7, device=dev, requires_grad=True)          # std_0 = 0.5
-    opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
     gamma, lam, clip, epochs, mb = 0.99, 0.95, 0.2, 4, 16384
     lay = RecordLayout([B], D, k)
     # The networks as the kernels see them, made once: the weights are the modules' own storage, so Adam's in-place steps are
@@ -69,12 +74,22 @@ def main():
     for net in (pol, cri):
         net.tensors['obs_shift'], net.tensors['obs_scale'] = shift, scale
     gp = gc = None                                                            # the gradients' buffers, reused by every call
+    if args.update == 'torch':
+        opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
+    else:                                                                     # the loss is  policy + 0.5 value
+        opt = Adam([dict(net=pol, log_std=log_std, std=std), dict(net=cri, scale=0.5)], lr=args.lr)
+    # what the graph reads is static: the records, returns, advantages and old log-probabilities are refilled in place
+    rec = torch.zeros((T, B, lay.F), device=dev)
+    ret, adv, logp_old = (torch.zeros((T, B), device=dev) for _ in range(3))
+    # one epoch = one replay: a permutation drawn into the graph's static buffer, then for every minibatch the two gradient
+    # launches and the Adam launch (clip and lr are baked into the graph; the capture's warm-up is undone by the constructor)
+    update = GraphedUpdate(lay, rec, adv, ret, logp_old, pol, cri, opt, mb, clip=clip) if args.update == 'graph' else None
     t_collect = t_fit = 0.0
     for it in range(args.iters):
         t0 = time.perf_counter()
         noise = torch.randn((T, B, k), device=dev)
         env.reset()
-        rec = env.rollout_packed(policy=pol, n_steps=T, noise=noise)          # ONE launch: T steps of B envs, [T, B, 2 D + k + 3]
+        env.rollout_packed(policy=pol, n_steps=T, noise=noise, out=rec)       # ONE launch: T steps of B envs, [T, B, 2 D + k + 3]
         c_avg, c_max, c_dq = env.get_constraints_logs()
         torch.cuda.synchronize()
         t_collect += time.perf_counter() - t0
@@ -83,11 +98,14 @@ def main():
         # V(next_obs), the log-probability of the drawn actions -- and then advantages, returns and PPO's normalisation, the
         # recurrence over time in one launch (returns.py), where a loop `for t in reversed(range(T))` costs five per step
         v, nv = values_from_records(lay, rec, cri)
-        ret, adv, _ = gae_from_records(lay, rec, v, nv, gamma, lam, normalize=True)
-        logp_old = log_prob_from_records(lay, rec, pol)
+        gae_from_records(lay, rec, v, nv, gamma, lam, normalize=True, out=(ret, adv))
+        logp_old.copy_(log_prob_from_records(lay, rec, pol))
         d = lay.unpack(rec)
         rew, last = d['reward'], d['last']
         for _ in range(epochs):
+            if update is not None:
+                update.replay()
+                continue
             perm = torch.randperm(T * B, device=dev)
             for i in range(0, T * B, mb):
                 idx = perm[i:i + mb]                                          # row numbers into the flat [T * B] records

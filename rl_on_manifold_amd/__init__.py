@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ('value_gradient', 'policy_gradient', 'value_gradient_from_records', 'policy_gradient_from_records', 'Gradients'):
         from . import fit
         return getattr(fit, name)
+    if name in ('Adam', 'GraphedUpdate'):
+        from . import optim
+        return getattr(optim, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

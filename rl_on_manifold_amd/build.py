@@ -13,7 +13,11 @@ EXTENSIONS holds what is built beside that table, in rows of the same kind: liba
 value losses, include/atacom_fit_hip.h), the eighth library.  It is not a row of TARGETS because the seven, their units, the
 files directly inside csrc/ and their kernel census are pinned by the tests that guard them against accidental growth; a
 library that only borrows headers by #include lives in a sub-directory of csrc/ (csrc/fit/) and in this second table, and
-build(), stale() and sources() take its key like any other.  build_all() builds the seven, build_extensions() the rest.
+build(), stale() and sources() take its key like any other.  build_all() builds the seven, build_extensions() the eighth.
+
+ADDITIONS is the third table and the open one: rows of the same kind, sources in a sub-directory of csrc/, and rows
+may be appended (EXTENSIONS is pinned at its one row too).  It holds libatacom_optim.so (the Adam step with its state on the device,
+include/atacom_optim_hip.h), the ninth library; build_additions() builds its rows.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
 than it.  The includes are read from the files themselves (sources()), so there is no list of headers to keep by hand.
@@ -42,9 +46,10 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 # float64 instantiations).  (-amdgpu-sched-strategy=max-ilp was tried per unit in round 1 -- planar step kernel -4 %, planar
 # policy-rollout kernel +19 %, iiwa quad kernel +8 % -- and dropped, profiles/r01_lanes_vs_batch.md; round 5: +0.7 % on the headline)
 # atacom_returns.hip: the fused multiply-adds of its recurrences are the explicit ones (include/atacom_returns_hip.h); the compiler
-# adds none
+# adds none.  atacom_optim.hip: every operation of the Adam step is the individually rounded one its header writes
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
-              'atacom_returns.hip': ['-ffp-contract=off']}
+              'atacom_returns.hip': ['-ffp-contract=off'],
+              'atacom_optim.hip': ['-ffp-contract=off']}
 
 # One row per library, keyed by its name: the units it compiles and `tuning`, whether it takes the ATACOM_ONLY_UNITS /
 # kept-object path below.  Everything else follows from the key (_binding.naming()).  A new library is a new row here, a
@@ -90,8 +95,21 @@ EXTENSIONS = {
 }
 
 
+ADDITIONS = {
+    'optim': _target('optim', ['atacom_optim.hip', 'atacom_optim_capi.cpp'], False, sub='optim'),
+}
+"""The open table: rows of the same kind as TARGETS and EXTENSIONS, and rows MAY BE APPENDED.  TARGETS and EXTENSIONS are
+pinned entry by entry by the tests that guard them; this one is checked row by row (each row's own properties, and that the
+table holds it), never by its length, so the next library is one more row here, a sub-directory of csrc/ and a binding module.
+'optim': the Adam step of an on-policy update with its state on the device (include/atacom_optim_hip.h); it borrows the host
+scaffolding by `#include "../..."` and adds no kernel or symbol to the other eight."""
+
+
 def _row(name):
-    return TARGETS[name] if name in TARGETS else EXTENSIONS[name]
+    for table in (TARGETS, EXTENSIONS, ADDITIONS):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
 
@@ -161,7 +179,7 @@ def _hipcc_version():
 
 
 def build(name='hip', force=False, verbose=True):
-    """Build the library `name` of TARGETS or EXTENSIONS if it is stale (or `force`) and return its path.  The main library is fourteen units
+    """Build the library `name` of TARGETS, EXTENSIONS or ADDITIONS if it is stale (or `force`) and return its path.  The main library is fourteen units
     and a few minutes, the policy and compact rollouts about a minute each, the others a few seconds."""
     target = _row(name)
     if not force and not stale(name):
@@ -196,5 +214,11 @@ def build_extensions(force=False, verbose=True):
     return [build(name, force, verbose) for name in EXTENSIONS]
 
 
+def build_additions(force=False, verbose=True):
+    """Every library of ADDITIONS, in its order; their paths."""
+    return [build(name, force, verbose) for name in ADDITIONS]
+
+
 if __name__ == '__main__':
-    print('\n'.join(build_all(force='--force' in sys.argv) + build_extensions(force='--force' in sys.argv)))
+    print('\n'.join(build_all(force='--force' in sys.argv) + build_extensions(force='--force' in sys.argv) +
+                    build_additions(force='--force' in sys.argv)))
