@@ -34,6 +34,10 @@ def __getattr__(name):
     if name in ('Adam', 'GraphedUpdate'):
         from . import optim
         return getattr(optim, name)
+    if name in ('fisher_vector_product', 'fisher_vector_product_from_records', 'natural_gradient', 'trpo_step', 'FisherProduct',
+                'CgWork'):
+        from . import trust
+        return getattr(trust, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

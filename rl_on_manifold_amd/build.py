@@ -17,7 +17,8 @@ build(), stale() and sources() take its key like any other.  build_all() builds 
 
 ADDITIONS is the third table and the open one: rows of the same kind, sources in a sub-directory of csrc/, and rows
 may be appended (EXTENSIONS is pinned at its one row too).  It holds libatacom_optim.so (the Adam step with its state on the device,
-include/atacom_optim_hip.h), the ninth library; build_additions() builds its rows.
+include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fisher-vector product of a TRPO policy step,
+include/atacom_trust_hip.h), the tenth; build_additions() builds its rows.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
 than it.  The includes are read from the files themselves (sources()), so there is no list of headers to keep by hand.
@@ -97,12 +98,15 @@ EXTENSIONS = {
 
 ADDITIONS = {
     'optim': _target('optim', ['atacom_optim.hip', 'atacom_optim_capi.cpp'], False, sub='optim'),
+    'trust': _target('trust', ['atacom_trust.hip', 'atacom_trust_capi.cpp'], False, sub='trust'),
 }
 """The open table: rows of the same kind as TARGETS and EXTENSIONS, and rows MAY BE APPENDED.  TARGETS and EXTENSIONS are
 pinned entry by entry by the tests that guard them; this one is checked row by row (each row's own properties, and that the
 table holds it), never by its length, so the next library is one more row here, a sub-directory of csrc/ and a binding module.
 'optim': the Adam step of an on-policy update with its state on the device (include/atacom_optim_hip.h); it borrows the host
-scaffolding by `#include "../..."` and adds no kernel or symbol to the other eight."""
+scaffolding by `#include "../..."` and adds no kernel or symbol to the other eight.
+'trust': the Fisher-vector product of a trust-region policy step (include/atacom_trust_hip.h); it borrows the network of
+atacom_policy.h, its host description, the host scaffolding and the view type of atacom_evaluate_hip.h, as 'fit' does."""
 
 
 def _row(name):

@@ -1,0 +1,149 @@
+// C-ABI host side of libatacom_trust.so (see include/atacom_trust_hip.h).  No handle: the device index travels in the call's
+// argument struct.  Validates, then dispatches to the launcher; contains no numerics.  The checks, their order and their words
+// are those of ../fit/atacom_fit_capi.cpp wherever the two libraries ask the same thing.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "atacom_trust.h"
+#define ATACOM_CAPI_E_HIP ATACOM_TRUST_E_HIP
+#include "../atacom_capi_common.h"   // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
+#include "../atacom_mlp_host.h"      // mlp_abi_copy
+
+namespace {
+
+std::string dec(long long v) { return std::to_string(v); }
+
+// [lo, hi) in bytes
+struct Extent {
+    intptr_t lo, hi;
+};
+
+Extent extent(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, int esize) {
+    int64_t lo = 0, hi = width - 1;
+    const int64_t so = n_outer > 1 ? v.stride_outer * (n_outer - 1) : 0, si = n_inner > 1 ? v.stride_inner * (n_inner - 1) : 0;
+    (so < 0 ? lo : hi) += so;
+    (si < 0 ? lo : hi) += si;
+    const intptr_t base = (intptr_t)v.ptr;
+    return {base + (intptr_t)(lo * esize), base + (intptr_t)((hi + 1) * esize)};
+}
+
+Extent flat(const void* p, int64_t bytes) { return {(intptr_t)p, (intptr_t)p + (intptr_t)bytes}; }
+
+bool overlap(const Extent& a, const Extent& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// rows must not run into each other; the view is an input and may repeat a row (stride 0)
+int check_strides(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, const char* name, const std::string& w) {
+    const struct { int64_t n, st; const char* dim; } dims[2] = {{n_outer, v.stride_outer, "stride_outer"}, {n_inner, v.stride_inner, "stride_inner"}};
+    for (const auto& d : dims) {
+        if (d.n <= 1) continue;
+        const int64_t mag = d.st < 0 ? -d.st : d.st;
+        if (mag >= width || d.st == 0) continue;
+        return fail(ATACOM_TRUST_E_INVALID, w + ": " + name + "." + d.dim + " = " + dec(d.st) + " is below the row width " + dec(width));
+    }
+    return ATACOM_TRUST_OK;
+}
+
+// Everything that decides the size of the workspace; *rows = M, *blocks = n_blocks_effective.
+int check_sizes(const atacom_trust_args* a, const std::string& w, atacom_mlp* net, int64_t* rows, int64_t* blocks) {
+    if (!a) return fail(ATACOM_TRUST_E_INVALID, w + ": null argument");
+    if (a->struct_size != sizeof(atacom_trust_args))
+        return fail(ATACOM_TRUST_E_INVALID, w + ": struct_size = " + dec(a->struct_size) + ", this library expects " + dec(sizeof(atacom_trust_args)));
+    if (a->device < 0) return fail(ATACOM_TRUST_E_INVALID, w + ": device = " + dec(a->device));
+    if (a->dtype != ATACOM_TRUST_F32 && a->dtype != ATACOM_TRUST_F64)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": no kernel for dtype " + dec(a->dtype));
+    if (a->n_outer < 1) return fail(ATACOM_TRUST_E_INVALID, w + ": n_outer must be >= 1, got " + dec(a->n_outer));
+    if (a->n_inner < 1) return fail(ATACOM_TRUST_E_INVALID, w + ": n_inner must be >= 1, got " + dec(a->n_inner));
+    if (a->n_outer > ATACOM_TRUST_MAX_ROWS / a->n_inner)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": n_outer * n_inner = " + dec(a->n_outer) + " * " + dec(a->n_inner) +
+                                                    " rows is too many (at most " + dec(ATACOM_TRUST_MAX_ROWS) + " a call)");
+    if (a->n_blocks < 0) return fail(ATACOM_TRUST_E_INVALID, w + ": n_blocks must be >= 1, or 0 for the library's choice, got " + dec(a->n_blocks));
+    if (a->n_blocks > ATACOM_TRUST_MAX_BLOCKS)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": n_blocks = " + dec(a->n_blocks) + " exceeds the launch grid (" + dec(ATACOM_TRUST_MAX_BLOCKS) + ")");
+    if (a->idx && a->n_idx < 1) return fail(ATACOM_TRUST_E_INVALID, w + ": n_idx must be >= 1 with idx, got " + dec(a->n_idx));
+    if (a->idx && a->n_idx > ATACOM_TRUST_MAX_ROWS)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": n_idx = " + dec(a->n_idx) + " rows is too many (at most " + dec(ATACOM_TRUST_MAX_ROWS) + " a call)");
+    // ---- the network
+    if (!atacom::mlp_abi_copy(&a->net, net))
+        return fail(ATACOM_TRUST_E_INVALID, w + ": net.struct_size = " + dec(a->net.struct_size) + ", this library expects " +
+                                                dec(sizeof(atacom_mlp)) + " or " + dec(ATACOM_MLP_SIZE_V1));
+    if (net->hidden != ATACOM_TRUST_HIDDEN)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": hidden = " + dec(net->hidden) + ", only 64 hidden units are supported");
+    if (net->n_in < 1 || net->n_in > ATACOM_TRUST_MAX_IN)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": n_in = " + dec(net->n_in) + " is outside 1 .. " + dec(ATACOM_TRUST_MAX_IN));
+    if (net->n_out < 1 || net->n_out > ATACOM_TRUST_MAX_OUT)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": n_out = " + dec(net->n_out) + " is outside 1 .. " + dec(ATACOM_TRUST_MAX_OUT));
+    *rows = a->idx ? a->n_idx : a->n_outer * a->n_inner;
+    *blocks = atacom_trust::effective_blocks(a->n_blocks, *rows, a->dtype == ATACOM_TRUST_F64);
+    return ATACOM_TRUST_OK;
+}
+
+size_t workspace_bytes(const atacom_trust_args* a, const atacom_mlp& net, int64_t blocks) {
+    const size_t raw = (size_t)blocks * (size_t)atacom_trust::net_size(net.n_in, net.n_out) * (a->dtype == ATACOM_TRUST_F64 ? 8 : 4);
+    return (raw + 255) / 256 * 256;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* atacom_trust_last_error(void) { return g_err.c_str(); }
+const char* atacom_trust_version(void) { return "atacom_trust 1.0 (gfx950)"; }
+
+size_t atacom_trust_workspace_size(const atacom_trust_args* a) {
+    atacom_mlp net;
+    int64_t rows = 0, blocks = 0;
+    if (check_sizes(a, "atacom_trust_workspace_size", &net, &rows, &blocks)) return 0;
+    return workspace_bytes(a, net, blocks);
+}
+
+int atacom_trust_fvp(const atacom_trust_args* a) {
+    const std::string w = "atacom_trust_fvp";
+    atacom_mlp net;
+    int64_t rows = 0, blocks = 0;
+    if (int rc = check_sizes(a, w, &net, &rows, &blocks)) return rc;
+    if (net.activation != 0 && net.activation != 1)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": activation = " + dec(net.activation) + " (0 = ReLU, 1 = tanh)");
+    if (!net.W1 || !net.b1 || !net.W2 || !net.b2 || !net.W3 || !net.b3)
+        return fail(ATACOM_TRUST_E_INVALID, w + ": null argument (a weight or bias of the network)");
+    if (net.sW1 || net.sb1 || net.sW2 || net.sb2 || net.sW3 || net.sb3)
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": a sigma network is not supported (the Fisher matrix is that of a state-independent std)");
+    if (net.squash) return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": squash is not supported (SAC's squashed policy is out of scope)");
+    if (net.mean_mode) return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": mean_mode = " + dec(net.mean_mode) + " is not supported");
+    if (net.explore) return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": explore = " + dec(net.explore) + " is not supported");
+    if (!net.std) return fail(ATACOM_TRUST_E_INVALID, w + ": null argument (net.std: the Fisher matrix needs the policy's std)");
+    // ---- the view, the direction and the outputs
+    if (!a->x.ptr) return fail(ATACOM_TRUST_E_INVALID, w + ": null argument (x)");
+    if (!a->v) return fail(ATACOM_TRUST_E_INVALID, w + ": null argument (v)");
+    if (!a->out || !a->workspace) return fail(ATACOM_TRUST_E_INVALID, w + ": null argument (out or workspace)");
+    if (!(a->damping >= 0.0) || !std::isfinite(a->damping))
+        return fail(ATACOM_TRUST_E_INVALID, w + ": damping must be >= 0 and finite, got " + std::to_string(a->damping));
+    const int64_t no = a->n_outer, ni = a->n_inner;
+    const int esize = a->dtype == ATACOM_TRUST_F64 ? 8 : 4;
+    if (int rc = check_strides(a->x, no, ni, net.n_in, "x", w)) return rc;
+    const size_t need = workspace_bytes(a, net, blocks);
+    if (a->workspace_bytes < need)
+        return fail(ATACOM_TRUST_E_INVALID, w + ": workspace_bytes = " + dec((long long)a->workspace_bytes) + " is below the " +
+                                                dec((long long)need) + " that atacom_trust_workspace_size gives");
+    const int64_t n_all = atacom_trust::net_size(net.n_in, net.n_out) + net.n_out;
+    const struct { const char* name; Extent e; } outs[2] = {{"out", flat(a->out, n_all * esize)}, {"workspace", flat(a->workspace, (int64_t)need)}};
+    const struct { const char* name; Extent e; bool used; } ins[3] = {
+        {"x", extent(a->x, no, ni, net.n_in, esize), true},
+        {"v", flat(a->v, n_all * esize), true},
+        {"idx", flat(a->idx, a->idx ? a->n_idx * 8 : 0), a->idx != nullptr}};
+    for (int o = 0; o < 2; ++o) {
+        for (const auto& in : ins)
+            if (in.used && overlap(outs[o].e, in.e)) return fail(ATACOM_TRUST_E_INVALID, w + ": " + outs[o].name + " overlaps " + in.name);
+        for (int p = 0; p < o; ++p)
+            if (overlap(outs[o].e, outs[p].e)) return fail(ATACOM_TRUST_E_INVALID, w + ": " + outs[p].name + " overlaps " + outs[o].name);
+    }
+
+    ON_DEVICE(a);
+    if (atacom_trust::trust_launch(*a, net, (int)blocks, rows, (hipStream_t)a->stream))
+        return fail(ATACOM_TRUST_E_UNSUPPORTED, w + ": no kernel for this call");
+    HIP_TRY(hipGetLastError());
+    return ATACOM_TRUST_OK;
+}
+
+}  // extern "C"
