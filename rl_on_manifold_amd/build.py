@@ -18,7 +18,8 @@ build(), stale() and sources() take its key like any other.  build_all() builds 
 ADDITIONS is the third table and the open one: rows of the same kind, sources in a sub-directory of csrc/, and rows
 may be appended (EXTENSIONS is pinned at its one row too).  It holds libatacom_optim.so (the Adam step with its state on the device,
 include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fisher-vector product of a TRPO policy step,
-include/atacom_trust_hip.h), the tenth; build_additions() builds its rows.
+include/atacom_trust_hip.h), the tenth; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
+it holds the headers that libatacom_fit.so and libatacom_trust.so share, which sources() finds through their #include lines.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
 than it.  The includes are read from the files themselves (sources()), so there is no list of headers to keep by hand.

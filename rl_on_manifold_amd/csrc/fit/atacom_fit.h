@@ -1,36 +1,17 @@
 // Launcher of libatacom_fit.so (include/atacom_fit_hip.h): what the C-ABI file calls after it has validated a call, and the
-// sizes both sides agree on.  The kernels are in atacom_fit.hip; nothing here touches the device.
+// sizes both sides agree on.  The kernels are in atacom_fit.hip; nothing here touches the device.  The workgroup and tile
+// constants, tiles() and effective_blocks() are those of ../mlp/atacom_mlp_backward.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../../include/atacom_fit_hip.h"
+#include "../mlp/atacom_mlp_backward.h"
 
 namespace atacom_fit {
 
-constexpr int kBlock = 256;                 // threads per workgroup: four wavefronts share one staged copy of the weights
-constexpr int kWaves = kBlock / 64;
-constexpr int kRowsF32 = 64;                // rows per wavefront and tile (four blocks of 16): the matrix-core form
-constexpr int kRowsF64 = 16;                // rows per WORKGROUP and tile: the vector form
-constexpr int kDefaultBlocks = 512;         // ceiling of the library's own choice of n_blocks (two workgroups per compute unit)
-constexpr int kReduceBlock = 256;            // threads of a k_fit_reduce workgroup: kReduceSlices slices of kReduceValues values
-constexpr int kReduceValues = 32;
-constexpr int kReduceSlices = kReduceBlock / kReduceValues;
+using namespace atacom_mlp_backward;
 
 // values of a gradient, and of one workgroup's partial (the d log std slots and the statistics are always there)
-__host__ __device__ inline int64_t grad_size(int n_in, int n_out) { return 64 * (int64_t)n_in + 64 + 4096 + 64 + 64 * n_out + n_out; }
+__host__ __device__ inline int64_t grad_size(int n_in, int n_out) { return net_size(n_in, n_out); }
 __host__ __device__ inline int64_t partial_size(int n_in, int n_out) { return grad_size(n_in, n_out) + n_out + ATACOM_FIT_STATS; }
-
-inline int64_t tiles(int64_t rows, bool f64) {
-    const int per = f64 ? kRowsF64 : kWaves * kRowsF32;
-    return (rows + per - 1) / per;
-}
-
-inline int64_t effective_blocks(int n_blocks, int64_t rows, bool f64) {
-    if (n_blocks > 0) return n_blocks;
-    const int64_t need = tiles(rows, f64);
-    return need < kDefaultBlocks ? need : kDefaultBlocks;
-}
 
 // Enqueue only; `net` has passed every check, `blocks` >= 1, `rows` = M.  Returns non-zero when there is no kernel.
 int fit_launch(const atacom_fit_args& a, const atacom_mlp& net, int blocks, int64_t rows, hipStream_t s);

@@ -1,6 +1,7 @@
 // C-ABI host side of libatacom_trust.so (see include/atacom_trust_hip.h).  No handle: the device index travels in the call's
 // argument struct.  Validates, then dispatches to the launcher; contains no numerics.  The checks, their order and their words
-// are those of ../fit/atacom_fit_capi.cpp wherever the two libraries ask the same thing.
+// are those of the gradient library's C-ABI file wherever the two libraries ask the same thing; the checks of the views are those
+// of ../mlp/atacom_view_checks.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -8,42 +9,12 @@
 
 #include "atacom_trust.h"
 #define ATACOM_CAPI_E_HIP ATACOM_TRUST_E_HIP
-#include "../atacom_capi_common.h"   // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
-#include "../atacom_mlp_host.h"      // mlp_abi_copy
+#define ATACOM_CAPI_E_INVALID ATACOM_TRUST_E_INVALID
+#include "../atacom_capi_common.h"        // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
+#include "../atacom_mlp_host.h"           // mlp_abi_copy
+#include "../mlp/atacom_view_checks.h"    // dec, Extent, extent, flat, overlap, check_strides
 
 namespace {
-
-std::string dec(long long v) { return std::to_string(v); }
-
-// [lo, hi) in bytes
-struct Extent {
-    intptr_t lo, hi;
-};
-
-Extent extent(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, int esize) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t so = n_outer > 1 ? v.stride_outer * (n_outer - 1) : 0, si = n_inner > 1 ? v.stride_inner * (n_inner - 1) : 0;
-    (so < 0 ? lo : hi) += so;
-    (si < 0 ? lo : hi) += si;
-    const intptr_t base = (intptr_t)v.ptr;
-    return {base + (intptr_t)(lo * esize), base + (intptr_t)((hi + 1) * esize)};
-}
-
-Extent flat(const void* p, int64_t bytes) { return {(intptr_t)p, (intptr_t)p + (intptr_t)bytes}; }
-
-bool overlap(const Extent& a, const Extent& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// rows must not run into each other; the view is an input and may repeat a row (stride 0)
-int check_strides(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, const char* name, const std::string& w) {
-    const struct { int64_t n, st; const char* dim; } dims[2] = {{n_outer, v.stride_outer, "stride_outer"}, {n_inner, v.stride_inner, "stride_inner"}};
-    for (const auto& d : dims) {
-        if (d.n <= 1) continue;
-        const int64_t mag = d.st < 0 ? -d.st : d.st;
-        if (mag >= width || d.st == 0) continue;
-        return fail(ATACOM_TRUST_E_INVALID, w + ": " + name + "." + d.dim + " = " + dec(d.st) + " is below the row width " + dec(width));
-    }
-    return ATACOM_TRUST_OK;
-}
 
 // Everything that decides the size of the workspace; *rows = M, *blocks = n_blocks_effective.
 int check_sizes(const atacom_trust_args* a, const std::string& w, atacom_mlp* net, int64_t* rows, int64_t* blocks) {

@@ -7,6 +7,7 @@ import os
 import abi_tools as abi
 
 OWN = {'atacom_fit.h', 'atacom_fit.hip', 'atacom_fit_capi.cpp', 'atacom_fit_hip.h'}
+SHARED = {'atacom_mlp_backward.h', 'atacom_view_checks.h'}          # csrc/mlp/: headers it shares with libatacom_trust.so
 
 
 def test_extensions_is_the_one_row():
@@ -32,11 +33,13 @@ def test_the_include_closure_follows_the_borrowed_headers_into_csrc():
     assert all(os.path.isabs(p) and os.path.isfile(p) for p in src)
     names = {os.path.basename(p) for p in src}
     assert OWN | {'atacom_policy.h', 'atacom_mlp_host.h', 'atacom_capi_common.h'} <= names
-    assert names == OWN | {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h',
-                           'atacom_hip.h', 'atacom_evaluate_hip.h'}
+    assert names == OWN | SHARED | {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h',
+                                    'atacom_hip.h', 'atacom_evaluate_hip.h'}
     # the borrowed files are the ones directly inside csrc/ and include/, not copies
     where = {os.path.basename(p): os.path.dirname(p) for p in src}
     assert where['atacom_policy.h'] == build.CSRC and where['atacom_fit_hip.h'] == abi.INCLUDE
+    for name in SHARED:
+        assert where[name] == os.path.join(build.CSRC, 'mlp'), name
     # it lends nothing: editing its files makes none of the seven stale
     for name, t in build.TARGETS.items():
         assert not OWN & {os.path.basename(p) for p in build.sources(t)}, name
@@ -60,6 +63,11 @@ def test_a_touched_file_makes_fit_stale_and_its_own_files_only_fit(monkeypatch):
     assert [n for n in every if build.stale(n)] == ['evaluate', 'fit']
     touched[:] = ['atacom_returns.hip']
     assert not build.stale('fit')
+    # the shared headers of csrc/mlp/: exactly fit and trust, none of the seven and not optim
+    libs += [t.lib for t in build.ADDITIONS.values()]
+    for name in sorted(SHARED):
+        touched[:] = [name]
+        assert [n for n in every + list(build.ADDITIONS) if build.stale(n)] == ['fit', 'trust'], name
 
 
 def test_the_seven_are_still_the_seven_and_build_extensions_builds_the_rest():
