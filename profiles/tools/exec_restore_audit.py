@@ -9,7 +9,11 @@ lane-0-only store block were placed at the top of the block's join label, i.e. B
 reopens the mask -- so only the lanes that ran the store block got their copy; the others read stale registers after the join.
 A vector write between a label and the exec restore that follows it executes under the narrowed mask of the region being
 closed; wave-wide values must not be copied there.  Flagged: a join label followed by NOTHING BUT register copies (and scalar
-bookkeeping) up to the `s_or_b64 exec, exec, ...` -- the body of a region (real work behind a label) is not.  Exit status 1 if any is found."""
+bookkeeping) up to the `s_or_b64 exec, exec, ...` -- the body of a region (real work behind a label) is not.  Scalar bookkeeping
+includes the spills of scalar registers into the lanes of a vector register (v_writelane_b32 / v_readlane_b32: they ignore
+the exec mask): the float64 rigid-body T-step kernel carried the defect BEHIND such spills -- the result of an inlined acos,
+copied to accumulation registers at the join of its |x| >= 0.5 region, stale in every lane with |x| < 0.5
+(profiles/rigid_body_limits.md) -- and an audit that took them for real work passed it.  Exit status 1 if any is found."""
 import re
 import sys
 
@@ -40,7 +44,7 @@ def audit(lines):
                 break
             if COPY.match(t) and '_dpp' not in t:
                 writes.append((j + 1, t.split('//')[0].strip()))
-            elif t and not t.startswith((';', '//', 's_', 'v_readlane', 'v_nop')) and not t.endswith(':'):
+            elif t and not t.startswith((';', '//', 's_', 'v_readlane', 'v_writelane', 'v_nop')) and not t.endswith(':'):
                 writes = None                 # real work between the label and the restore: the body of a region, not a join
                 break
             j -= 1

@@ -87,6 +87,15 @@ __device__ __forceinline__ T joint7_target(const T (&Y)[3], const T (&Z)[3], T q
     const T sgn = abig ? (ax[0] * Z[0] + ax[1] * Z[1] + ax[2] * Z[2]) * ian : Z[2];   // axis . z, axis = (0,0,1) fallback
     target *= sgn;                                                                // :161
     const T pi = T(3.14159265358979323846);
+    if constexpr (std::is_same<T, double>::value) {
+        // :163-166 as selects in the float64 kernels (at the register ceiling): a branch here is one more region at whose
+        // join hipcc 7.2 can place the register allocator's copies under the narrowed exec mask (num<double>::acos,
+        // atacom_linalg.h: with acos branch-free the copies of `target` moved to this join in the quad T-step kernel).  The
+        // float32 kernels keep the text they were measured with.
+        const T off = target - q7_cur;
+        const T shift = (off > pi / 2) ? -pi : ((off < -pi / 2) ? pi : T(0));
+        return target + shift;
+    }
     if (target - q7_cur > pi / 2) target -= pi;                                   // :163-166
     else if (target - q7_cur < -pi / 2) target += pi;
     return target;

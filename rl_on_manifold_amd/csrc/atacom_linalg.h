@@ -98,7 +98,29 @@ template <> struct num<double> {
     static __device__ __forceinline__ double log(double x) { return ::log(x); }
     static __device__ __forceinline__ double tanh(double x) { return ::tanh(x); }
     static __device__ __forceinline__ void sincos(double x, double* s, double* c) { ::sincos(x, s, c); }
-    static __device__ __forceinline__ double acos(double x) { return ::acos(x); }
+    // acos WITHOUT a branch.  The library's acos(double) evaluates |x| >= 0.5 in a region of its own (a narrowed exec mask);
+    // in the rigid-body T-step kernels at the register ceiling hipcc 7.2 copied its result to accumulation registers at the
+    // JOIN of that region, in front of the exec restore: every lane with |x| < 0.5 kept a stale servo set-point
+    // (tests/test_gpu_rigid_limits.py found it; the defect of profiles/r06_exec_mask_copies.md, audited by
+    // tests/test_kernel_resources.py).  The same argument reduction and the rational approximation of asin on [0, 0.5]
+    // (fdlibm's e_acos.c: R(z) = z P(z) / Q(z), |error| < 2^-58.75), both ranges evaluated by selects: within 1 ulp of pi of
+    // the library's result on [-1, 1]; the callers clamp x to that interval.
+    static __device__ __forceinline__ double acos(double x) {
+        constexpr double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
+        const double y = __builtin_fabs(x);
+        const bool big = y >= 0.5;
+        const double z = big ? __builtin_fma(y, -0.5, 0.5) : x * x;
+        const double p = z * (1.66666666666666657415e-01 + z * (-3.25565818622400915405e-01 + z * (2.01212532134862925881e-01 +
+                         z * (-4.00555345006794114027e-02 + z * (7.91534994289814532176e-04 + z * 3.47933107596021167570e-05)))));
+        const double q = 1.0 + z * (-2.40339491173441421878e+00 + z * (2.02094576023350569471e+00 +
+                         z * (-6.88283971605453293030e-01 + z * 7.70381505559019352791e-02)));
+        const double r = p / q;
+        const double s = big ? __builtin_sqrt(z) : x;
+        const double t = 2.0 * (s + s * r);                                          // |x| >= 0.5: 2 asin(sqrt((1 - |x|) / 2))
+        const double far = (x < 0.0) ? 2.0 * pio2_hi - (t - 2.0 * pio2_lo) : t;
+        const double near = pio2_hi - (x - (pio2_lo - x * r));
+        return big ? far : near;
+    }
     static __device__ __forceinline__ double max(double a, double b) { return fmax(a, b); }
     static __device__ __forceinline__ double min(double a, double b) { return fmin(a, b); }
     static __device__ __forceinline__ double clamp(double x, double lo, double hi) { return fmin(fmax(x, lo), hi); }

@@ -247,16 +247,20 @@ REPRO_SCALES = parity_tools.QUICK_SCALES + parity_tools.DEEP_SCALES[2:]
 REPRO_DRAWS = 64
 
 
-def recorder32(step_fn=step_outputs, seed=5):
-    """A recorder of the float32 rule, its constants unchanged, with the wider audit draws above."""
-    return parity_tools.SensitivityRecorder(step_fn, seed=seed, stacked_draws=True, repro_scales=REPRO_SCALES,
-                                            repro_draws=REPRO_DRAWS, repro_structured=True)
+ARM_FIELDS = ('q', 'dq', 's', 'puck')           # the state the probes perturb (SensitivityRecorder's own default)
 
 
-def recorder64(step_fn=step_outputs, seed=6):
+def recorder32(step_fn=step_outputs, seed=5, state_fields=ARM_FIELDS):
+    """A recorder of the float32 rule, its constants unchanged, with the wider audit draws above.  state_fields: the state
+    the probes perturb (tests/rigid_limit_cases.py adds the servo joints' qx, dqx)."""
+    return parity_tools.SensitivityRecorder(step_fn, seed=seed, state_fields=state_fields, stacked_draws=True,
+                                            repro_scales=REPRO_SCALES, repro_draws=REPRO_DRAWS, repro_structured=True)
+
+
+def recorder64(step_fn=step_outputs, seed=6, state_fields=ARM_FIELDS):
     """A recorder of the float64 rule (module constants above)."""
-    return parity_tools.SensitivityRecorder(step_fn, seed=seed, quick_scales=F64_QUICK_SCALES, deep_scales=F64_DEEP_SCALES,
-                                            floor=F64_BOUND, jc_noise=False, stacked_draws=True)
+    return parity_tools.SensitivityRecorder(step_fn, seed=seed, state_fields=state_fields, quick_scales=F64_QUICK_SCALES,
+                                            deep_scales=F64_DEEP_SCALES, floor=F64_BOUND, jc_noise=False, stacked_draws=True)
 
 
 def shares(p, n=None):

@@ -146,9 +146,11 @@ def _rigid_body_env_step(dt, lanes, mode, T):
 @pytest.mark.parametrize('lanes', [1, 4])
 @pytest.mark.parametrize('dt', ['f64', 'f32'])
 def test_rigid_body_env_step_against_oracle(dt, lanes, mode):
-    """dynamics_mode = 'rigid_body' / 'rigid_body_ff': the whole env step (ATACOM projection, inverse dynamics, effort saturation, servo
-    joints, hybrid forward dynamics, integration) vs the oracle, teacher-forced incl. the servo-joint state, on both mappings
-    the mode has.  float64: 256 x 30 states at 1e-8.  float32: 256 x 8 states by the sensitivity rule (its host side -- the
+    """dynamics_mode = 'rigid_body' / 'rigid_body_ff': the whole env step (ATACOM projection, inverse dynamics, servo joints,
+    hybrid forward dynamics, integration) vs the oracle, teacher-forced incl. the servo-joint state, on both mappings the mode
+    has.  Of the step's saturations these closed-loop states reach the servo velocity set-point clip only: the motor limit,
+    its floor and the arm effort limits never bind here (largest |tau| 140 Nm against 320) -- tests/test_gpu_rigid_limits.py
+    runs the states where they do.  float64: 256 x 30 states at 1e-8.  float32: 256 x 8 states by the sensitivity rule (its host side -- the
     oracle's rigid-body step under perturbations -- is what takes the time: the 30-step form is the `slow` test below)."""
     _rigid_body_env_step(dt, lanes, mode, 30 if dt == 'f64' else 8)
 

@@ -154,7 +154,10 @@ def test_no_register_copies_under_a_narrowed_exec_mask(tmp_path):
     of four lanes when built without the LDS parking (the flagged kernel is exactly the one that fails on hardware,
     profiles/r06_nopark_policy_tests.log).  The defect is silent and moves with code generation, so EVERY kernel of the built
     library is disassembled and audited for the pattern (profiles/tools/exec_restore_audit.py): a join label followed by
-    nothing but vector copies up to the exec restore."""
+    nothing but vector copies up to the exec restore -- spills of scalar registers into vector lanes (v_writelane_b32, which
+    ignores the mask) between them do not hide it: behind such spills the float64 rigid-body T-step kernel (one environment
+    per lane, hold_q) lost the result of the library's acos in every lane with |x| < 0.5, which
+    tests/test_gpu_rigid_limits.py found on hardware (profiles/rigid_body_limits.md); num<double>::acos is branch-free since."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, 'profiles', 'tools'))
     from exec_restore_audit import audit_library
@@ -162,3 +165,21 @@ def test_no_register_copies_under_a_narrowed_exec_mask(tmp_path):
     found, n_objects = audit_library(build.build(verbose=False), str(tmp_path), LLVM)
     assert n_objects >= 13
     assert not found, [(f[1], [t for _, t in f[4]]) for f in found]
+
+
+def test_the_exec_audit_sees_copies_behind_lane_spills():
+    """The join block as the float64 rigid-body T-step kernel had it (disassembly abridged): the copies of a wave-wide value
+    sit between the label and the exec restore together with spills of scalar registers into vector lanes.  Flagged; the body
+    of a region (real vector work behind a label) is not."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'profiles', 'tools'))
+    from exec_restore_audit import audit
+    join = ['00000000000d1900 <_ZN6atacom9k_rolloutIdNS_4IiwaELi1ELb1ELb1ELi0ELb0EEEvNS_6ParamsIT_EEiPS3_PiPKS3_S5_S5_S5_>:',
+            '\ts_and_saveexec_b64 s[36:37], vcc', '\ts_cbranch_execz L708', '\tv_cndmask_b32_e32 v128, 0, v22, vcc',
+            '00000000000f1578 <L708>:', '\ts_mov_b32 s73, s71', '\tv_writelane_b32 v255, s72, 47',
+            '\tv_accvgpr_write_b32 a175, v129', '\tv_accvgpr_write_b32 a174, v128', '\tv_writelane_b32 v255, s73, 48',
+            '\ts_nop 1', '\ts_or_b64 exec, exec, s[36:37]']
+    found = audit(join)
+    assert len(found) == 1 and [t for _, t in found[0][3]] == ['v_accvgpr_write_b32 a175, v129', 'v_accvgpr_write_b32 a174, v128']
+    body = join[:5] + ['\tv_mul_f64 v[20:21], v[222:223], v[222:223]'] + join[5:]
+    assert audit(body) == []
