@@ -2,6 +2,7 @@
 perturbed initial states (bench.feasible_init), random actions, auto-reset, free-running -- over many launches: what a
 launch lasts (HIP events), what its median and its slowest wavefront compute, and (canonical chart) how often the
 data-dependent parts run.  Needs the -DATACOM_TIMESTAMPS build: ATACOM_LIB=build/ts/libatacom_ts.so python profiles/tools/gpu_bench_probe.py [lanes]
+MB_ENV=planar probes the planar environment (default iiwa), MB_BATCH the batch (default 8192).
 """
 import os, sys
 import numpy as np
@@ -15,10 +16,11 @@ B = int(os.environ.get('MB_BATCH', 8192))
 chart = os.environ.get('MB_CHART', 'reference')
 dev = torch.device('cuda:0')
 gen = torch.Generator(device=dev); gen.manual_seed(1234)
-env, init, rej = bench.make_env('iiwa', B, dev, gen, lanes, chart_mode=chart, dynamics_mode=os.environ.get('MB_DYN', 'kinematic'))
+name = os.environ.get('MB_ENV', 'iiwa')
+env, init, rej = bench.make_env(name, B, dev, gen, lanes, chart_mode=chart, dynamics_mode=os.environ.get('MB_DYN', 'kinematic'))
 L = env.lanes_per_env
-acts = torch.rand((64, B, 5), device=dev, generator=gen) * 2 - 1
-obs, rew = torch.empty((B, 18), device=dev), torch.empty((B,), device=dev)
+acts = torch.rand((64, B, env.dims['null']), device=dev, generator=gen) * 2 - 1
+obs, rew = torch.empty((B, env.obs_dim), device=dev), torch.empty((B,), device=dev)
 ab, last = torch.empty((B,), device=dev, dtype=torch.uint8), torch.empty((B,), device=dev, dtype=torch.uint8)
 for i in range(100):
     env.step_into(acts[i % 64], obs, rew, ab, last)
@@ -47,7 +49,7 @@ for rep in range(N):
             print('   last launch, least squares on wave compute time: %.2f us per stiff-row trip, %.2f per stage A trip, %.2f per '
                   'stage B, %.2f base' % tuple(coef))
 r = np.array(rows)
-print('%s chart, lanes %d, B %d, %d launches on the bench workload (us): events mean %.1f / min %.1f / max %.1f / std %.2f | '
+print(name + ', %s chart, lanes %d, B %d, %d launches on the bench workload (us): events mean %.1f / min %.1f / max %.1f / std %.2f | '
       'last wave starts %.2f | load %.2f | compute: median wave %.2f, p90 %.2f, slowest %.2f | store %.2f | last store lands %.2f'
       % (chart, L, B, N, r[:, 0].mean(), r[:, 0].min(), r[:, 0].max(), r[:, 0].std(), r[:, 1].mean(), r[:, 2].mean(),
          r[:, 3].mean(), r[:, 5].mean(), r[:, 4].mean(), r[:, 7].mean(), r[:, 6].mean()))

@@ -1203,6 +1203,55 @@ __device__ __forceinline__ void env_step(const Params<T>& P, EnvState<T, E>& st,
     out.last = out.absorbing || (st.t >= Q.horizon);
 }
 
+// ------------------------------------------------------------------ the kernel arguments in one round trip
+// The compiler puts each scalar load of a kernel argument into the basic block that first uses it, and the bounds check, the
+// mask test and the masked-out exit cut the top of k_step into four blocks: a wave made FIVE scalar round trips to the
+// kernel-argument segment, one after the other, in front of its first arithmetic instruction (the batch size; the state
+// pointers; mask and the output pointers; action; the rest of Params), and four of them asked for a 64-byte line that no
+// earlier trip had requested -- a kernel starts with cold caches, so each of those went to memory
+// (profiles/step_entry.md).  kernarg_request_lines asks, in the entry block in front of the bounds check and next to the
+// batch size, for the four pointers that the loads at the top go through (state, integer record, action, mask) and for one
+// dword of every 64-byte line of the segment: one trip brings every line in; the state, statistics and action loads follow
+// it directly, and the trips that remain (the output pointers, the rest of Params) stay in their blocks and hit the scalar
+// cache while the state is on its way.  The dwords go nowhere (an empty asm takes them) and the pointers are the ones the
+// kernel holds anyway, so no register is added.  BYTES is the size of the explicit arguments: the reads stay inside them.
+// (Holding the arguments themselves live from the entry block, as whole 16-dword blocks, was built first: 36 bytes of
+// scratch per lane in the headline kernel.  Scalar loads written by hand in inline asm are not an option: the compiler's
+// wait counters do not see them.)
+template <typename T>
+constexpr int STEP_KERNARG_BYTES = (int)((sizeof(Params<T>) + 7) / 8 * 8 + 8 * sizeof(void*));       // k_step: Params, 8 pointers
+template <int BYTES>
+__device__ __forceinline__ void kernarg_request_lines(const void* p0, const void* p1, const void* p2, const void* p3) {
+    static_assert(BYTES % 4 == 0, "whole dwords");
+    const auto* w = (const __attribute__((address_space(4))) unsigned int*)__builtin_amdgcn_kernarg_segment_ptr();
+    constexpr int LINES = (BYTES + 63) / 64;
+    static_assert(64 * (LINES - 1) + 4 <= BYTES, "the last read is inside the explicit arguments");
+    unsigned int v[LINES];
+#pragma unroll
+    for (int i = 1; i < LINES; ++i) v[i] = w[16 * i];         // line 0 holds the batch size, which the kernel reads itself
+    // (every load in front of the first asm: a load written next to its own asm is issued behind the previous one's wait)
+    asm volatile("" :: "s"(p0), "s"(p1), "s"(p2), "s"(p3));
+#pragma unroll
+    for (int i = 1; i < LINES; ++i) asm volatile("" :: "s"(v[i]));
+}
+// Selected per instantiation in the way of PARAMS_REREAD: on where registers, scratch and LDS are the parent's
+// (profiles/tools/kernel_table_diff.py on the two builds, profiles/step_entry.md).  The 23 below are the instantiations whose
+// register allocation or scratch size moved with it, by a few registers or bytes either way -- 16 of them kernels with a
+// private segment to begin with; they keep the parent's text and the parent's machine code.
+constexpr bool entry_lines_moved(bool f64, int env, int ln, bool hold, bool dyn, int chart, bool noise) {
+    const int key = ln * 10000 + hold * 1000 + dyn * 100 + chart * 10 + noise;       // lanes | held q | rigid body | chart | noise
+    constexpr int IIWA_F64[] = {10001, 10010, 10011, 10100, 11001, 11011, 11100, 40011, 40110, 41010, 41110,
+                                80001, 80010, 80011, 81010, 81011};
+    constexpr int PLANAR_F64[] = {10010};
+    constexpr int IIWA_F32[] = {11100, 20000, 21001, 21010, 41000, 41001};
+    if (f64 && env == Iiwa::ID) { for (int k : IIWA_F64) if (k == key) return true; }
+    if (f64 && env == Planar::ID) { for (int k : PLANAR_F64) if (k == key) return true; }
+    if (!f64 && env == Iiwa::ID) { for (int k : IIWA_F32) if (k == key) return true; }
+    return false;
+}
+template <typename T, typename E, int LN, bool HOLD, bool DYN, int CHART, bool NOISE>
+constexpr bool ENTRY_LINES = !entry_lines_moved(std::is_same<T, double>::value, E::ID, LN, HOLD, DYN, CHART, NOISE);
+
 // ------------------------------------------------------------------ kernels
 // mask (nullable): environments whose byte is 0 sit the call out -- state, step counter and statistics untouched; they
 // report their current observation, reward 0, absorbing 0, last 0 (a vectorised Core's finished environments).
@@ -1215,15 +1264,17 @@ __global__ void __launch_bounds__(BLOCK<LANES>) k_step(const Params<T> P, T* __r
     // longer wait for a scalar load before their first state loads, but the step time did not move (27.5 us both ways)
     // and the launch-bound circle kernel got slower, 7.4 -> 10.7 us: profiles/r02_lanes_vs_batch.md)
     using L = Planes<E>;
+#ifdef ATACOM_TIMESTAMPS        // tuning build only (profiles/tools/gpu_phase_probe.py): 100 MHz wall-clock stamps per phase
+    // (the first one is the wave's first instruction: the "load" phase holds every trip to the kernel arguments)
+    const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    if constexpr (ENTRY_LINES<T, E, LANES, HOLD, DYN, CHART, NOISE>) kernarg_request_lines<STEP_KERNARG_BYTES<T>>(f, ip, action, mask);
     const int B = P.batch;
     const int gt = blockIdx.x * BLOCK<LANES> + threadIdx.x;
     const int b = gt / LANES;                  // whole quads leave together (BLOCK % LANES == 0)
     const int lq = gt % LANES;
     if (b >= B) return;
     const EnvRef<T, NOISE> ref{f, ip, B, b, true};
-#ifdef ATACOM_TIMESTAMPS        // tuning build only (profiles/tools/gpu_phase_probe.py): 100 MHz wall-clock stamps per phase
-    const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
-#endif
     EnvState<T, E> st;
     load_state<T, E>(f, ip, B, b, st);
     if (mask && mask[b] == 0) {                // whole lane groups leave together (the mask is per environment)
