@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""Minimal on-GPU TD3 on the batched ATACOM tasks -- an end-to-end use of the off-policy half of the engine.
+
+Not part of the hot path: the reference trains with MushroomRL's TD3 (examples/iiwa_air_hockey_exp.py: build_agent_td3), which
+is not installed here.  This script shows the same loop shape on the engine: collection = ONE kernel launch per iteration (the
+actor's squashed mean + clipped Gaussian exploration + ATACOM env step, `MlpPolicy.from_td3` inside `rollout_packed`), the
+records go into a `ReplayMemory` on the device, and for each fit a minibatch of row numbers is drawn (`sample`), the TD target
+r + gamma (1 - absorbing) min_j Q'_j(s', clip(pi'(s') + clip(sigma eps))) is ONE launch that reads the memory in place
+(`ReplayMemory.td_target`), the critic and actor losses are torch autograd on `columns(idx)`, torch's Adam steps, and the three target networks
+move in ONE launch (`soft_update`).  `--target torch` computes the same targets with torch modules -- the gather, three module
+passes and a dozen elementwise kernels that `td_target` replaces -- for comparison.  The time per stage is printed (host clock
+around a device synchronise, the first iteration left out as warm-up).
+
+    python examples/td3_air_hockey.py --env planar --iters 10
+"""
+import argparse
+import copy
+import os
+import sys
+import time
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere in the checkout
+from rl_on_manifold_amd import (BatchedAtacomEnv, BatchedPointReachEnv, MlpPolicy, QCritic, RecordLayout, ReplayMemory,
+                                soft_update)
+
+
+class Actor(nn.Module):                    # the layer names of the reference's TD3ActorNetwork
+    def __init__(self, n_in, n_out, scaling, h=64):
+        super().__init__()
+        self._h1, self._h2, self._h3 = nn.Linear(n_in, h), nn.Linear(h, h), nn.Linear(h, n_out)
+        self.register_buffer('_action_scaling', scaling.clone())
+
+    def forward(self, x):
+        return self._action_scaling * torch.tanh(self._h3(torch.relu(self._h2(torch.relu(self._h1(x))))))
+
+
+class Critic(nn.Module):                   # the layer names of the reference's TD3CriticNetwork: the action enters twice
+    def __init__(self, n_obs, n_act, scaling, h=64):
+        super().__init__()
+        self._h1, self._h2_s, self._h2_a, self._h3 = (nn.Linear(n_obs + n_act, h), nn.Linear(h, h), nn.Linear(n_act, h, bias=False),
+                                                      nn.Linear(h, 1))
+        self.register_buffer('_action_scaling', scaling.clone())
+
+    def forward(self, s, a):
+        a = a / self._action_scaling
+        h1 = torch.relu(self._h1(torch.cat((s, a), -1)))
+        return self._h3(torch.relu(self._h2_s(h1) + self._h2_a(a))).squeeze(-1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--env', default='planar', choices=['planar', 'iiwa', 'point'])
+    ap.add_argument('--batch', type=int, default=4096)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--steps', type=int, default=16, help='environment steps per iteration and environment')
+    ap.add_argument('--fits', type=int, default=16, help='minibatches per iteration')
+    ap.add_argument('--minibatch', type=int, default=16384)
+    ap.add_argument('--capacity', type=int, default=1 << 20)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--target', default='fused', choices=['fused', 'torch'], help="'torch': the targets through torch modules")
+    args = ap.parse_args()
+    torch.manual_seed(args.seed)
+    dev = torch.device('cuda:0')
+    B, T = args.batch, args.steps
+    if args.env == 'point':
+        env = BatchedPointReachEnv(B, device=dev, horizon=200, seed=args.seed)
+    else:
+        env = BatchedAtacomEnv(args.env, B, device=dev, auto_reset=True, horizon=120, random_init=True, seed=args.seed)
+    D, k = env.obs_dim, env.dims['null']
+    gamma, tau, sigma, noise_std, noise_clip, delay = 0.99, 5e-3, 0.1, 0.2, 0.5, 2
+    scaling = torch.ones(k, device=dev)
+    low, high = -scaling, scaling.clone()
+    actor = Actor(D, k, scaling).to(dev)
+    critics = [Critic(D, k, scaling).to(dev) for _ in range(2)]
+    actor_t, critics_t = copy.deepcopy(actor), [copy.deepcopy(c) for c in critics]
+
+    def as_policy(net):                    # the weights are the module's own storage: Adam's in-place steps are seen by the kernels
+        pol = MlpPolicy.from_td3(net, sigma ** 2, low=-1.0, high=1.0)
+        pol.tensors.update(act_scale=scaling, act_low=low, act_high=high, std=torch.full((k,), sigma, device=dev))
+        return pol
+
+    def as_critic(net):
+        c = QCritic.from_module(net, D)
+        c.tensors['act_scale'] = scaling
+        return c
+
+    pol, pol_t = as_policy(actor), as_policy(actor_t)
+    cri, cri_t = [as_critic(c) for c in critics], [as_critic(c) for c in critics_t]
+    opt_a = torch.optim.Adam(actor.parameters(), lr=1e-4)
+    opt_c = torch.optim.Adam([p for c in critics for p in c.parameters()], lr=3e-4)
+    lay = RecordLayout([B], D, k)
+    mem = ReplayMemory(args.capacity, D, k, device=dev)
+    rec = torch.zeros((T, B, lay.F), device=dev)
+    y = torch.empty(args.minibatch, device=dev)
+    times = dict(collect=0.0, add=0.0, sample=0.0, target=0.0, losses=0.0, soft_update=0.0)
+
+    warm = [args.iters > 1]                # the first iteration loads code objects and lets the libraries pick algorithms: not timed
+
+    def timed(name, fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        if not warm[0]:
+            times[name] += time.perf_counter() - t0
+        return out
+
+    def torch_target(idx, eps):
+        with torch.no_grad():
+            c = mem.columns(idx)
+            a = actor_t(c['next_obs'])
+            a = torch.minimum(torch.maximum(a + torch.clamp(noise_std * eps, -noise_clip, noise_clip), low), high)
+            q = torch.minimum(critics_t[0](c['next_obs'], a), critics_t[1](c['next_obs'], a))
+            return c['reward'] + gamma * (q * (1.0 - c['absorbing']))
+
+    n_fit = timed_iters = timed_fits = 0
+    env.reset()
+    for it in range(args.iters):
+        noise = torch.randn((T, B, k), device=dev)
+        timed('collect', lambda: env.rollout_packed(policy=pol, n_steps=T, noise=noise, out=rec))
+        timed('add', lambda: mem.add(lay, rec))
+        q_loss = a_loss = float('nan')
+        for _ in range(args.fits):
+            idx = timed('sample', lambda: mem.sample(args.minibatch))
+            eps = torch.randn((args.minibatch, k), device=dev)
+            if args.target == 'fused':
+                timed('target', lambda: mem.td_target(pol_t, cri_t, idx, gamma, eps=eps, noise_std=noise_std, noise_clip=noise_clip,
+                                                      low=low, high=high, out=y))
+                tgt = y
+            else:
+                tgt = timed('target', lambda: torch_target(idx, eps))
+
+            def losses():
+                c = mem.columns(idx)
+                lq = sum(((cr(c['obs'], c['action']) - tgt) ** 2).mean() for cr in critics)
+                opt_c.zero_grad(set_to_none=True)
+                lq.backward()
+                opt_c.step()
+                la = None
+                if n_fit % delay == 0:
+                    la = -critics[0](c['obs'], actor(c['obs'])).mean()
+                    opt_a.zero_grad(set_to_none=True)
+                    la.backward()
+                    opt_a.step()
+                return lq, la
+            lq, la = timed('losses', losses)
+            timed('soft_update', lambda: soft_update([pol_t] + cri_t, [pol] + cri, tau))
+            n_fit += 1
+            q_loss, a_loss = lq.item(), (a_loss if la is None else la.item())
+        timed_iters = timed_iters + (0 if warm[0] else 1)
+        timed_fits = timed_fits + (0 if warm[0] else args.fits)
+        warm[0] = False
+        r = rec[..., lay.fields['reward']]
+        print('iter %3d  memory %8d  reward/step %8.4f  critic loss %10.4f  actor loss %10.4f' % (it, mem.size, r.mean().item(), q_loss, a_loss),
+              flush=True)
+    n, ni = max(timed_fits, 1), max(timed_iters, 1)
+    print('per iteration (%d timed): collect %.3f ms, add %.3f ms;  per fit (%d rows, targets: %s): sample %.3f ms, target %.3f ms, '
+          'losses + Adam %.3f ms, soft update %.3f ms' % (ni, 1e3 * times['collect'] / ni, 1e3 * times['add'] / ni, args.minibatch,
+                                                          args.target, 1e3 * times['sample'] / n, 1e3 * times['target'] / n,
+                                                          1e3 * times['losses'] / n, 1e3 * times['soft_update'] / n))
+
+
+if __name__ == '__main__':
+    main()

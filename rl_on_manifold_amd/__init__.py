@@ -38,6 +38,9 @@ def __getattr__(name):
                 'CgWork'):
         from . import trust
         return getattr(trust, name)
+    if name in ('QCritic', 'q_values', 'td_target', 'soft_update', 'ReplayMemory'):
+        from . import offpolicy
+        return getattr(offpolicy, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

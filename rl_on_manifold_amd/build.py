@@ -18,7 +18,8 @@ build(), stale() and sources() take its key like any other.  build_all() builds 
 ADDITIONS is the third table and the open one: rows of the same kind, sources in a sub-directory of csrc/, and rows
 may be appended (EXTENSIONS is pinned at its one row too).  It holds libatacom_optim.so (the Adam step with its state on the device,
 include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fisher-vector product of a TRPO policy step,
-include/atacom_trust_hip.h), the tenth; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
+include/atacom_trust_hip.h), the tenth, and libatacom_offpolicy.so (the critic's Q-value, the fused TD target and the soft target
+update of DDPG and TD3, include/atacom_offpolicy_hip.h), the eleventh; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
 it holds the headers that libatacom_fit.so and libatacom_trust.so share, which sources() finds through their #include lines.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
@@ -48,10 +49,12 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 # float64 instantiations).  (-amdgpu-sched-strategy=max-ilp was tried per unit in round 1 -- planar step kernel -4 %, planar
 # policy-rollout kernel +19 %, iiwa quad kernel +8 % -- and dropped, profiles/r01_lanes_vs_batch.md; round 5: +0.7 % on the headline)
 # atacom_returns.hip: the fused multiply-adds of its recurrences are the explicit ones (include/atacom_returns_hip.h); the compiler
-# adds none.  atacom_optim.hip: every operation of the Adam step is the individually rounded one its header writes
+# adds none.  atacom_optim.hip: every operation of the Adam step is the individually rounded one its header writes; so are the
+# target arithmetic and the soft update of atacom_offpolicy.hip (the fused multiply-adds of its float64 networks are explicit)
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
               'atacom_returns.hip': ['-ffp-contract=off'],
-              'atacom_optim.hip': ['-ffp-contract=off']}
+              'atacom_optim.hip': ['-ffp-contract=off'],
+              'atacom_offpolicy.hip': ['-ffp-contract=off']}
 
 # One row per library, keyed by its name: the units it compiles and `tuning`, whether it takes the ATACOM_ONLY_UNITS /
 # kept-object path below.  Everything else follows from the key (_binding.naming()).  A new library is a new row here, a
@@ -100,6 +103,7 @@ EXTENSIONS = {
 ADDITIONS = {
     'optim': _target('optim', ['atacom_optim.hip', 'atacom_optim_capi.cpp'], False, sub='optim'),
     'trust': _target('trust', ['atacom_trust.hip', 'atacom_trust_capi.cpp'], False, sub='trust'),
+    'offpolicy': _target('offpolicy', ['atacom_offpolicy.hip', 'atacom_offpolicy_capi.cpp'], False, sub='offpolicy'),
 }
 """The open table: rows of the same kind as TARGETS and EXTENSIONS, and rows MAY BE APPENDED.  TARGETS and EXTENSIONS are
 pinned entry by entry by the tests that guard them; this one is checked row by row (each row's own properties, and that the
@@ -107,7 +111,10 @@ table holds it), never by its length, so the next library is one more row here, 
 'optim': the Adam step of an on-policy update with its state on the device (include/atacom_optim_hip.h); it borrows the host
 scaffolding by `#include "../..."` and adds no kernel or symbol to the other eight.
 'trust': the Fisher-vector product of a trust-region policy step (include/atacom_trust_hip.h); it borrows the network of
-atacom_policy.h, its host description, the host scaffolding and the view type of atacom_evaluate_hip.h, as 'fit' does."""
+atacom_policy.h, its host description, the host scaffolding and the view type of atacom_evaluate_hip.h, as 'fit' does.
+'offpolicy': the forward half of a DDPG / TD3 update (include/atacom_offpolicy_hip.h); it borrows the LDS layouts of
+atacom_policy.h, the host description of a network, the host scaffolding and the view type of atacom_evaluate_hip.h, and nothing
+of csrc/mlp/, 'fit', 'trust' or 'optim'."""
 
 
 def _row(name):
