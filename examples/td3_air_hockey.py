@@ -6,8 +6,11 @@ is not installed here.  This script shows the same loop shape on the engine: col
 actor's squashed mean + clipped Gaussian exploration + ATACOM env step, `MlpPolicy.from_td3` inside `rollout_packed`), the
 records go into a `ReplayMemory` on the device, and for each fit a minibatch of row numbers is drawn (`sample`), the TD target
 r + gamma (1 - absorbing) min_j Q'_j(s', clip(pi'(s') + clip(sigma eps))) is ONE launch that reads the memory in place
-(`ReplayMemory.td_target`), the critic and actor losses are torch autograd on `columns(idx)`, torch's Adam steps, and the three target networks
-move in ONE launch (`soft_update`).  `--target torch` computes the same targets with torch modules -- the gather, three module
+(`ReplayMemory.td_target`), the gradients of the two critic losses are ONE launch and that of the actor loss another
+(`ReplayMemory.critic_gradient`, `actor_gradient`: the memory read in place again), torch's Adam steps the critics from
+`QGradients.to_module` and the device `Adam` steps the actor, and the three target networks move in ONE launch (`soft_update`).
+`--losses torch` takes the losses through torch autograd on `columns(idx)` instead -- the gather, three forward and three
+backward passes that the two gradient calls replace -- for comparison.  `--target torch` computes the same targets with torch modules -- the gather, three module
 passes and a dozen elementwise kernels that `td_target` replaces -- for comparison.  The time per stage is printed (host clock
 around a device synchronise, the first iteration left out as warm-up).
 
@@ -23,7 +26,7 @@ import torch
 import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))   # run from anywhere in the checkout
-from rl_on_manifold_amd import (BatchedAtacomEnv, BatchedPointReachEnv, MlpPolicy, QCritic, RecordLayout, ReplayMemory,
+from rl_on_manifold_amd import (Adam, BatchedAtacomEnv, BatchedPointReachEnv, MlpPolicy, QCritic, RecordLayout, ReplayMemory,
                                 soft_update)
 
 
@@ -61,6 +64,7 @@ def main():
     ap.add_argument('--capacity', type=int, default=1 << 20)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--target', default='fused', choices=['fused', 'torch'], help="'torch': the targets through torch modules")
+    ap.add_argument('--losses', default='fused', choices=['fused', 'torch'], help="'torch': the losses through torch autograd")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     dev = torch.device('cuda:0')
@@ -91,6 +95,8 @@ def main():
     cri, cri_t = [as_critic(c) for c in critics], [as_critic(c) for c in critics_t]
     opt_a = torch.optim.Adam(actor.parameters(), lr=1e-4)
     opt_c = torch.optim.Adam([p for c in critics for p in c.parameters()], lr=3e-4)
+    opt_a_dev = Adam([{'net': pol}], lr=1e-4) if args.losses == 'fused' else None      # steps the actor's own storage, in one launch
+    grads = dict(q=None, a=None)
     lay = RecordLayout([B], D, k)
     mem = ReplayMemory(args.capacity, D, k, device=dev)
     rec = torch.zeros((T, B, lay.F), device=dev)
@@ -146,7 +152,21 @@ def main():
                     la.backward()
                     opt_a.step()
                 return lq, la
-            lq, la = timed('losses', losses)
+
+            def fused_losses():
+                first = grads['q'] is None
+                grads['q'] = mem.critic_gradient(cri, idx, tgt, out=grads['q'])
+                if first:                  # the parameters share the buffers from here on: every later call rewrites their .grad
+                    for g, net in zip(grads['q'], critics):
+                        g.to_module(net)
+                opt_c.step()
+                la = None
+                if n_fit % delay == 0:
+                    grads['a'] = mem.actor_gradient(pol, cri[0], idx, out=grads['a'])
+                    opt_a_dev.step(grads['a'])
+                    la = grads['a'].loss
+                return grads['q'][0].loss + grads['q'][1].loss, la
+            lq, la = timed('losses', fused_losses if args.losses == 'fused' else losses)
             timed('soft_update', lambda: soft_update([pol_t] + cri_t, [pol] + cri, tau))
             n_fit += 1
             q_loss, a_loss = lq.item(), (a_loss if la is None else la.item())
@@ -157,9 +177,9 @@ def main():
         print('iter %3d  memory %8d  reward/step %8.4f  critic loss %10.4f  actor loss %10.4f' % (it, mem.size, r.mean().item(), q_loss, a_loss),
               flush=True)
     n, ni = max(timed_fits, 1), max(timed_iters, 1)
-    print('per iteration (%d timed): collect %.3f ms, add %.3f ms;  per fit (%d rows, targets: %s): sample %.3f ms, target %.3f ms, '
+    print('per iteration (%d timed): collect %.3f ms, add %.3f ms;  per fit (%d rows, targets: %s, losses: %s): sample %.3f ms, target %.3f ms, '
           'losses + Adam %.3f ms, soft update %.3f ms' % (ni, 1e3 * times['collect'] / ni, 1e3 * times['add'] / ni, args.minibatch,
-                                                          args.target, 1e3 * times['sample'] / n, 1e3 * times['target'] / n,
+                                                          args.target, args.losses, 1e3 * times['sample'] / n, 1e3 * times['target'] / n,
                                                           1e3 * times['losses'] / n, 1e3 * times['soft_update'] / n))
 
 

@@ -41,6 +41,9 @@ def __getattr__(name):
     if name in ('QCritic', 'q_values', 'td_target', 'soft_update', 'ReplayMemory'):
         from . import offpolicy
         return getattr(offpolicy, name)
+    if name in ('critic_gradient', 'actor_gradient', 'QGradients'):
+        from . import offgrad
+        return getattr(offgrad, name)
     if name in ('BatchedPointReachEnv', 'PointReachAtacom'):
         from . import point
         return getattr(point, name)

@@ -19,7 +19,8 @@ ADDITIONS is the third table and the open one: rows of the same kind, sources in
 may be appended (EXTENSIONS is pinned at its one row too).  It holds libatacom_optim.so (the Adam step with its state on the device,
 include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fisher-vector product of a TRPO policy step,
 include/atacom_trust_hip.h), the tenth, and libatacom_offpolicy.so (the critic's Q-value, the fused TD target and the soft target
-update of DDPG and TD3, include/atacom_offpolicy_hip.h), the eleventh; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
+update of DDPG and TD3, include/atacom_offpolicy_hip.h), the eleventh, and libatacom_offgrad.so (the critic and actor gradients of a
+DDPG / TD3 update, include/atacom_offgrad_hip.h), the twelfth; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
 it holds the headers that libatacom_fit.so and libatacom_trust.so share, which sources() finds through their #include lines.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
@@ -50,11 +51,13 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 # policy-rollout kernel +19 %, iiwa quad kernel +8 % -- and dropped, profiles/r01_lanes_vs_batch.md; round 5: +0.7 % on the headline)
 # atacom_returns.hip: the fused multiply-adds of its recurrences are the explicit ones (include/atacom_returns_hip.h); the compiler
 # adds none.  atacom_optim.hip: every operation of the Adam step is the individually rounded one its header writes; so are the
-# target arithmetic and the soft update of atacom_offpolicy.hip (the fused multiply-adds of its float64 networks are explicit)
+# target arithmetic and the soft update of atacom_offpolicy.hip (the fused multiply-adds of its float64 networks are explicit) and
+# the row arithmetic of atacom_offgrad.hip (squash, its derivative, the division by act_scale, the head)
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
               'atacom_returns.hip': ['-ffp-contract=off'],
               'atacom_optim.hip': ['-ffp-contract=off'],
-              'atacom_offpolicy.hip': ['-ffp-contract=off']}
+              'atacom_offpolicy.hip': ['-ffp-contract=off'],
+              'atacom_offgrad.hip': ['-ffp-contract=off']}
 
 # One row per library, keyed by its name: the units it compiles and `tuning`, whether it takes the ATACOM_ONLY_UNITS /
 # kept-object path below.  Everything else follows from the key (_binding.naming()).  A new library is a new row here, a
@@ -104,6 +107,7 @@ ADDITIONS = {
     'optim': _target('optim', ['atacom_optim.hip', 'atacom_optim_capi.cpp'], False, sub='optim'),
     'trust': _target('trust', ['atacom_trust.hip', 'atacom_trust_capi.cpp'], False, sub='trust'),
     'offpolicy': _target('offpolicy', ['atacom_offpolicy.hip', 'atacom_offpolicy_capi.cpp'], False, sub='offpolicy'),
+    'offgrad': _target('offgrad', ['atacom_offgrad.hip', 'atacom_offgrad_capi.cpp'], False, sub='offgrad'),
 }
 """The open table: rows of the same kind as TARGETS and EXTENSIONS, and rows MAY BE APPENDED.  TARGETS and EXTENSIONS are
 pinned entry by entry by the tests that guard them; this one is checked row by row (each row's own properties, and that the
@@ -114,7 +118,9 @@ scaffolding by `#include "../..."` and adds no kernel or symbol to the other eig
 atacom_policy.h, its host description, the host scaffolding and the view type of atacom_evaluate_hip.h, as 'fit' does.
 'offpolicy': the forward half of a DDPG / TD3 update (include/atacom_offpolicy_hip.h); it borrows the LDS layouts of
 atacom_policy.h, the host description of a network, the host scaffolding and the view type of atacom_evaluate_hip.h, and nothing
-of csrc/mlp/, 'fit', 'trust' or 'optim'."""
+of csrc/mlp/, 'fit', 'trust' or 'optim'.
+'offgrad': the backward half of a DDPG / TD3 update (include/atacom_offgrad_hip.h); it borrows what 'offpolicy' borrows, declares
+its own critic descriptor and carries its own backward pass: nothing of csrc/mlp/, 'fit', 'trust', 'optim' or 'offpolicy'."""
 
 
 def _row(name):

@@ -1,0 +1,1066 @@
+// Kernels of libatacom_offgrad.so (include/atacom_offgrad_hip.h states the arithmetic): k_offgrad_critic<T, CH>, the forward and
+// the backward pass of one or two two-branch critics over the rows of a minibatch; k_offgrad_actor<T, CH>, the deterministic
+// policy gradient -- actor forward, critic forward and input gradient, actor forward again and backward, as phases of a
+// workgroup; and k_offgrad_reduce<T>, which adds the workgroups' partial sums in a fixed order.
+//
+// Borrowed from ../atacom_policy.h, which this unit includes and does not edit: the LDS layout MlpLdsM, the operand mapping of
+// mlp_forward_mfma, mlp_act16, mlp_act, wave_lds_fence and num<T>.  The backward pass is this unit's own: layer 2 of the critic
+// has two branches, so dW2a = sum delta2 as^T rides on dW2's A operands, TD3's dW1 covers the as columns of [xn | as], and the
+// actor call needs the critic's INPUT gradient, W2a^T delta2 (+ W1[:, D:]^T delta1), which no weight-gradient pass produces.
+//
+// Float32 mappings, one wavefront, one block of 16 rows (lane = (n16, g) = (lane % 16, lane / 16)):
+//   * transposed, H^T = W X^T: lane (n16, g) holds, in register v of tile t, unit 16 t + 4 g + v of row n16 -- for h1, h2 and,
+//     computed the same way from W3^T and W2^T, for delta2 and delta1; the input gradient comes out the same way, element
+//     4 g + v of row n16;
+//   * the weight gradients have the ROW as the K index, so both operands go once through a [16 rows][64 units] buffer of the
+//     wavefront's staging area (put / get, the column rotated by 16 (row % 4) against bank conflicts);
+//   * the accumulators (Grads) stay in registers for the whole walk; at its end the bias sums are added across lanes,
+//     wavefronts 1, 2, 3 hand their registers to wavefront 0 through LDS in that order and wavefront 0 stores the partial.
+// LDS: one network block MlpLdsM<4 CH, 64, 8>::NET with W2a [64][8] in rows 8 .. 15 of its W3 block (whose outputs are never
+// stored), 8 floats, and 8 KB of staging per wavefront: 63808 bytes.  The kernels are bound to one wavefront per SIMD.
+//
+// The walk of the critic kernel is per wavefront (no barrier between staging and hand-over); the walk of the actor kernel is
+// uniform per workgroup, because it restages behind barriers.  Loads are not predicated per lane: a lane past the end reads the
+// last row again, its dy is zero and its stores are guarded.  No atomics, plain vector stores.
+// Compiled with -ffp-contract=off (build.UNIT_FLAGS): the row arithmetic is the individually rounded one the header writes;
+// the fused multiply-adds of the float64 kernels are explicit.
+#include "atacom_offgrad.h"
+#include "../atacom_policy.h"
+
+namespace atacom_offgrad {
+
+typedef atacom::mfma_v4f V4;
+constexpr int kExtra = 8;         // floats after the network block, unused: the block and the staging keep their offsets
+constexpr int kStage = 2048;      // floats of staging per wavefront: two [16][64] transposition buffers
+
+template <typename T>
+struct Rows {
+    const T* p;
+    int64_t so, si;
+};
+
+template <typename T>
+struct Net {
+    const T *W1, *b1, *W2, *b2, *W2a, *W3, *b3, *shift, *scale, *act_scale;
+    int n1, n_out, activation, mean_mode;
+};
+
+template <typename T>
+struct CriticParams {
+    Net<T> net[2];
+    int kind, n_obs, n_act;
+    int64_t n_rows, n_inner;
+    const int64_t* idx;
+    Rows<T> obs, action;
+    const T* target;
+    int64_t target_stride;
+    T* workspace;
+};
+
+template <typename T>
+struct ActorParams {
+    Net<T> actor, critic;
+    int kind, n_obs, n_act;
+    int64_t n_rows, n_inner;
+    const int64_t* idx;
+    Rows<T> obs;
+    T *aout, *dqout;
+    int64_t aout_stride, dqout_stride;
+    T* workspace;
+};
+
+// the flat number of the call's row r; a row past the end is the last one again
+template <typename P>
+__device__ __forceinline__ int64_t flat_row(const P& p, int64_t r) {
+    const int64_t last = p.n_rows - 1;
+    r = r < last ? r : last;
+    return p.idx ? p.idx[r] : r;
+}
+
+// the host admits at most 2^31 - 1 rows, so the row's (outer, inner) index is a 32-bit division; the offsets are 64-bit
+template <typename T>
+__device__ __forceinline__ const T* row_ptr(const Rows<T>& v, int64_t fr, int64_t n_inner) {
+    const uint32_t o = (uint32_t)fr / (uint32_t)n_inner, i = (uint32_t)fr - o * (uint32_t)n_inner;
+    return v.p + (int64_t)o * v.so + (int64_t)i * v.si;
+}
+
+struct Offsets {
+    int b1, W2, b2, W3, b3, W2a, end;
+};
+
+__host__ __device__ __forceinline__ Offsets offsets(int n_in, int n_out, int n_act) {
+    Offsets o;
+    o.b1 = H * n_in; o.W2 = o.b1 + H; o.b2 = o.W2 + H * H; o.W3 = o.b2 + H; o.b3 = o.W3 + H * n_out; o.W2a = o.b3 + n_out;
+    o.end = o.W2a + H * n_act;
+    return o;
+}
+
+// ------------------------------------------------------------------------------------------------------------ float32
+template <int CH>
+struct LdsM : atacom::MlpLdsM<4 * CH, H, NK> {
+    using L = atacom::MlpLdsM<4 * CH, H, NK>;
+    static constexpr int W2A = L::W3 + 8 * L::S2;      // [64][8]
+    static constexpr int AUX = L::EXPLORE;             // act_scale [8]
+    static_assert(H * 8 <= 8 * L::S2, "W2a fits the unread half of the W3 block");
+};
+
+// Every word a phase reads is written here, the padding as zero: the W1 slots at or past n1 (the actor's n_in = D <= 4 CH), the
+// W3 rows and biases from n_out to 7, the W2a columns at or past n_act (all of them for the actor).
+template <int CH>
+__device__ __forceinline__ void stage_net(const Net<float>& n, int n_obs, int n_act, float* lds, int tid) {
+    using L = LdsM<CH>;
+    __syncthreads();                                   // the phase before has read its weights
+    // The actor kernel stages inside its loop over the rounds.  Left visible, the per-thread source addresses of every staging
+    // iteration (they divide by n1) are hoisted out of that loop as 64-bit pairs and spill to scratch; an opaque thread index
+    // keeps them where they are used.
+    asm volatile("" : "+v"(tid));
+    for (int i = tid; i < H * L::S1; i += kBlock) {      // [unit][g][8], slot s of group g = element CH g + s
+        const int u = i / L::S1, g = (i % L::S1) / 8, s = i % 8, e = CH * g + s;
+        lds[L::W1 + i] = (s < CH && e < n.n1) ? n.W1[u * n.n1 + e] : 0.0f;
+    }
+    for (int i = tid; i < H * H; i += kBlock) lds[L::W2 + (i / H) * L::S2 + (i % H)] = n.W2[i];
+    for (int i = tid; i < 8 * H; i += kBlock) lds[L::W3 + (i / H) * L::S2 + (i % H)] = i < n.n_out * H ? n.W3[i] : 0.0f;
+    for (int i = tid; i < 8 * L::S2; i += kBlock) {      // rows 8 .. 15 of the W3 block: W2a [64][8], then zeros
+        const int u = i / 8, k = i % 8;
+        lds[L::W2A + i] = (n.W2a && u < H && k < n_act) ? n.W2a[u * n_act + k] : 0.0f;
+    }
+    for (int i = tid; i < H; i += kBlock) { lds[L::B1 + i] = n.b1[i]; lds[L::B2 + i] = n.b2[i]; }
+    for (int i = tid; i < 16; i += kBlock) lds[L::B3 + i] = i < n.n_out ? n.b3[i] : 0.0f;
+    for (int i = tid; i < 32; i += kBlock) {             // [g][8] like W1; past the observation: shift 0, scale 1
+        const int g = i / 8, s = i % 8, e = CH * g + s;
+        const bool real = s < CH && e < n_obs;
+        lds[L::SHIFT + i] = (real && n.shift) ? n.shift[e] : 0.0f;
+        lds[L::SCALE + i] = (real && n.scale) ? n.scale[e] : 1.0f;
+    }
+    for (int i = tid; i < 8; i += kBlock) lds[L::AUX + i] = (i < n_act && n.act_scale) ? n.act_scale[i] : 1.0f;
+    __syncthreads();
+}
+
+// element e of the normalised observation of the row at xr; 0 at or past n_obs.  The load is under the full exec mask.
+template <int CH>
+__device__ __forceinline__ float obs_elem(const float* lds, const float* xr, int e, int n_obs) {
+    using L = LdsM<CH>;
+    const int ec = e < n_obs ? e : n_obs - 1;
+    const int slot = 8 * (ec / CH) + ec % CH;
+    const float v = (xr[ec] - lds[L::SHIFT + slot]) * lds[L::SCALE + slot];
+    return e < n_obs ? v : 0.0f;
+}
+
+// element k of as = a / act_scale of the row at ar; 0 outside 0 .. n_act - 1
+template <int CH>
+__device__ __forceinline__ float as_elem(const float* lds, const float* ar, int k, int n_act) {
+    using L = LdsM<CH>;
+    const int kc = k < 0 ? 0 : (k < n_act ? k : n_act - 1);
+    const float v = ar[kc] / lds[L::AUX + kc];
+    return (k >= 0 && k < n_act) ? v : 0.0f;
+}
+
+// element e of the critic's first-layer input x1 = xn (DDPG) | [xn | as] (TD3, `cat`)
+template <int CH>
+__device__ __forceinline__ float x1_elem(const float* lds, const float* xr, const float* ar, int e, int n_obs, int n_act, bool cat) {
+    const float x = obs_elem<CH>(lds, xr, e, n_obs), a = as_elem<CH>(lds, ar, cat ? e - n_obs : -1, n_act);
+    return e < n_obs ? x : a;
+}
+
+// The forward pass of one block of 16 rows, keeping what the backward pass needs.  xin[s] = element CH g + s of the input of
+// row n16; aop[j] = as[4 j + g] of row n16, the B operand of the `ka` action steps of layer 2 (0 for the actor).  h1, h2: the
+// activations; o: register v = output 4 g + v of row n16 (real for 4 g + v < n_out).
+template <int CH>
+__device__ __forceinline__ void forward_block(const float* __restrict__ net, const float (&xin)[CH], const float (&aop)[2], int ka,
+                                              int activation, int n16, int g, V4 (&h1)[4], V4 (&h2)[4], V4& o) {
+    using L = LdsM<CH>;
+    const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    float w1[4][8];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        h1[t] = *reinterpret_cast<const V4*>(net + L::B1 + 16 * t + 4 * g);
+        const float* row = net + L::W1 + (16 * t + n16) * L::S1 + 8 * g;
+        const V4 lo = *reinterpret_cast<const V4*>(row), hi = *reinterpret_cast<const V4*>(row + 4);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { w1[t][s] = lo[s]; w1[t][4 + s] = hi[s]; }
+    }
+#pragma unroll
+    for (int s = 0; s < CH; ++s)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) h1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[t][s], xin[s], h1[t], 0, 0, 0);
+    atacom::mlp_act16(h1, activation);
+    // ---- layer 2: K-step (t, v) carries unit 16 t + 4 g + v, i.e. register v of h1[t]; then the action steps
+#pragma unroll
+    for (int u = 0; u < 4; ++u) h2[u] = *reinterpret_cast<const V4*>(net + L::B2 + 16 * u + 4 * g);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        V4 w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = *reinterpret_cast<const V4*>(net + L::W2 + (16 * u + n16) * L::S2 + 16 * t + 4 * g);
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) h2[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[u][v], h1[t][v], h2[u], 0, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (j < ka) {                                   // wave-uniform
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                h2[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(net[L::W2A + (16 * u + n16) * 8 + 4 * j + g], aop[j], h2[u], 0, 0, 0);
+        }
+    }
+    atacom::mlp_act16(h2, activation);
+    // ---- output layer: rows >= n_out of W3 are zero, rows 8 .. 15 hold W2a and their outputs are not used
+    V4 oa = *reinterpret_cast<const V4*>(net + L::B3 + 4 * g), ob = zero;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const V4 w = *reinterpret_cast<const V4*>(net + L::W3 + n16 * L::S2 + 16 * t + 4 * g);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            if ((t & 1) == 0) oa = __builtin_amdgcn_mfma_f32_16x16x4f32(w[v], h2[t][v], oa, 0, 0, 0);
+            else ob = __builtin_amdgcn_mfma_f32_16x16x4f32(w[v], h2[t][v], ob, 0, 0, 0);
+        }
+    }
+    o = oa + ob;
+}
+
+// The transposition buffer [16 rows][64 units]: written from the accumulator layout, read as (row, unit) with the lanes of a
+// read on consecutive units.
+__device__ __forceinline__ void put(float* buf, const V4 (&h)[4], int n16, int g) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) *reinterpret_cast<V4*>(buf + n16 * 64 + ((16 * t + 4 * g + 16 * (n16 & 3)) & 63)) = h[t];
+}
+
+__device__ __forceinline__ float get(const float* buf, int row, int unit) {
+    return buf[row * 64 + ((unit + 16 * (row & 3)) & 63)];
+}
+
+// delta <- delta * act'(a), from the activation h = act(a) itself; one wave-uniform branch
+__device__ __forceinline__ void times_act_prime(V4 (&d)[4], const V4 (&h)[4], int activation) {
+    if (activation == 0) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) d[t][v] = h[t][v] > 0.0f ? d[t][v] : 0.0f;
+    } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) d[t][v] *= __builtin_fmaf(-h[t][v], h[t][v], 1.0f);
+    }
+}
+
+__device__ __forceinline__ float sum16(float v) {      // over the 16 lanes that share lane / 16, in every one of them
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__device__ __forceinline__ float sum64(float v) {      // over the wavefront, in every lane
+    v = sum16(v);
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// a wavefront's accumulators of a network's gradient, for the whole walk; WA: with dW2a (a critic)
+template <int NT, bool WA>
+struct Grads {
+    V4 acc1[4][NT], acc2[4][4], acc2a[4], acc3[4], db1[4], db2[4];
+    static constexpr int kSlots = 16 * (NT + 7 + (WA ? 1 : 0));     // registers of a lane = slots of the hand-over
+
+    __device__ __forceinline__ void zero() {
+        const V4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            acc2a[t] = acc3[t] = db1[t] = db2[t] = z;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc2[t][u] = z;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc1[t][nt] = z;
+        }
+    }
+};
+
+// The backward pass of a block whose dy lies in LDS, [16 rows][8] at t_del + 128 (written by this wavefront, not yet fenced):
+// dW3, delta2, dW2 (and dW2a), delta1, dW1 and the bias gradients into `a`.  xb[s][nt] = element 16 nt + n16 of the first
+// layer's input of row 4 s + g of the block, asb[s] = as[n16] of that row: the B operands whose K index is the row.  t_act and
+// t_del are the wavefront's two transposition buffers, free again when it returns.
+template <int CH, int NT, bool WA>
+__device__ __forceinline__ void backward_block(const float* lds, float* t_act, float* t_del, const V4 (&h1)[4], const V4 (&h2)[4],
+                                               const float (&xb)[4][NT], const float (&asb)[4], int activation, int n16, int g,
+                                               Grads<NT, WA>& a) {
+    using L = LdsM<CH>;
+    const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    put(t_act, h2, n16, g);                                  // dW3's B operand; dy is its A operand
+    atacom::wave_lds_fence();
+    // ---- dW3[k][j] += sum_rows dy[row][k] h2[row][j]: M = k (n16 < 8), N = j, K = the row 4 s + g
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const float ld = t_del[128 + (4 * s + g) * 8 + (n16 & 7)];
+        const float x = n16 < 8 ? ld : 0.0f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            a.acc3[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, get(t_act, 4 * s + g, 16 * u + n16), a.acc3[u], 0, 0, 0);
+    }
+    // ---- delta2 = (W3^T dy) * act'(a2): M = unit, N = row n16, K = the output 4 s + g
+    V4 da[4] = {zero, zero, zero, zero};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const float b = t_del[128 + n16 * 8 + 4 * s + g];       // dy[4 s + g] of this lane's own row
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            da[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[L::W3 + (4 * s + g) * L::S2 + 16 * u + n16], b, da[u], 0, 0, 0);
+    }
+    times_act_prime(da, h2, activation);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a.db2[u] += da[u];
+    atacom::wave_lds_fence();                            // dW3 has read both buffers
+    put(t_del, da, n16, g);
+    put(t_act, h1, n16, g);
+    atacom::wave_lds_fence();
+    // ---- dW2[j][i] += sum_rows delta2[row][j] h1[row][i];  dW2a[j][k] += sum_rows delta2[row][j] as[row][k]
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        float x[4], b[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { x[t] = get(t_del, 4 * s + g, 16 * t + n16); b[t] = get(t_act, 4 * s + g, 16 * t + n16); }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) a.acc2[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], b[u], a.acc2[t][u], 0, 0, 0);
+            if constexpr (WA) a.acc2a[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], asb[s], a.acc2a[t], 0, 0, 0);
+        }
+    }
+    // ---- delta1 = (W2^T delta2) * act'(a1): K-step (u, v) carries unit j = 16 u + 4 g + v, i.e. register v of da[u]
+    V4 d1[4] = {zero, zero, zero, zero};
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const float* wrow = lds + L::W2 + (16 * u + 4 * g + v) * L::S2 + n16;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) d1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[16 * t], da[u][v], d1[t], 0, 0, 0);
+        }
+    times_act_prime(d1, h1, activation);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) a.db1[t] += d1[t];
+    atacom::wave_lds_fence();                            // dW2 has read the deltas
+    put(t_del, d1, n16, g);
+    atacom::wave_lds_fence();
+    // ---- dW1[j][e] += sum_rows delta1[row][j] x1[row][e]
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        float x[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) x[t] = get(t_del, 4 * s + g, 16 * t + n16);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) a.acc1[t][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], xb[s][nt], a.acc1[t][nt], 0, 0, 0);
+    }
+    atacom::wave_lds_fence();                            // before the next block writes over the deltas
+}
+
+// the wavefront's sums of the bias gradients over the rows (lane % 16)
+template <int NT, bool WA>
+__device__ __forceinline__ void sum_biases(Grads<NT, WA>& a) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { a.db1[t][v] = sum16(a.db1[t][v]); a.db2[t][v] = sum16(a.db2[t][v]); }
+}
+
+// The workgroup's sums: wavefronts 1, 2, 3 hand their registers to wavefront 0 through LDS, in that order.  Every register of
+// every lane is handed over, [slot][lane]: the kSlots of `a` first, then the kernel's own -- own(f, q) applies x = f(q++, x) to
+// each of them.  The caller asserts that the slots fit the workgroup's LDS.
+template <int NT, bool WA, typename Own>
+__device__ __forceinline__ void hand_over(Grads<NT, WA>& a, float* lds, int wave, int lane, Own&& own) {
+    auto each = [&](auto&& f) {
+        int q = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) a.acc1[t][nt][v] = f(q++, a.acc1[t][nt][v]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) a.acc2[t][u][v] = f(q++, a.acc2[t][u][v]);
+                if constexpr (WA) a.acc2a[t][v] = f(q++, a.acc2a[t][v]);
+                a.acc3[t][v] = f(q++, a.acc3[t][v]);
+                a.db1[t][v] = f(q++, a.db1[t][v]);
+                a.db2[t][v] = f(q++, a.db2[t][v]);
+            }
+        own(f, q);
+    };
+    __syncthreads();
+    for (int w = 1; w < kWaves; ++w) {
+        if (wave == w) each([&](int q, float v) { lds[q * 64 + lane] = v; return v; });
+        __syncthreads();
+        if (wave == 0) each([&](int q, float v) { return v + lds[q * 64 + lane]; });
+        __syncthreads();
+    }
+}
+
+// the partial up to db2 and dW2a, in the layout of the gradient: plain vector stores.  db3 and the statistics are the kernel's.
+template <int NT, bool WA>
+__device__ __forceinline__ void store_net(const Grads<NT, WA>& a, float* out, int n_in, int n_out, int n_act, int n16, int g) {
+    const Offsets o = offsets(n_in, n_out, n_act);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int j = 16 * t + 4 * g + v;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                if (16 * nt + n16 < n_in) out[j * n_in + 16 * nt + n16] = a.acc1[t][nt][v];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) out[o.W2 + j * H + 16 * u + n16] = a.acc2[t][u][v];
+            if (4 * g + v < n_out) out[o.W3 + (4 * g + v) * H + 16 * t + n16] = a.acc3[t][v];
+            if constexpr (WA)
+                if (n16 < n_act) out[o.W2a + j * n_act + n16] = a.acc2a[t][v];
+            if (n16 == 0) { out[o.b1 + j] = a.db1[t][v]; out[o.b2 + j] = a.db2[t][v]; }
+        }
+}
+
+template <int CH>
+__device__ __forceinline__ void critic_f32(const CriticParams<float>& p) {
+    constexpr int NT = 4 * CH > 16 ? 2 : 1;
+    using L = LdsM<CH>;
+    constexpr int kLds = L::NET + kExtra + kWaves * kStage;
+    __shared__ __attribute__((aligned(16))) float lds[kLds];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n16 = lane & 15, g = lane >> 4;
+    // (selected field by field, not indexed: a run-time index into the kernel's argument block would put it in scratch)
+    Net<float> net;
+    const bool second = blockIdx.y != 0;
+#define OFFGRAD_PICK(f) net.f = second ? p.net[1].f : p.net[0].f
+    OFFGRAD_PICK(W1); OFFGRAD_PICK(b1); OFFGRAD_PICK(W2); OFFGRAD_PICK(b2); OFFGRAD_PICK(W2a); OFFGRAD_PICK(W3); OFFGRAD_PICK(b3);
+    OFFGRAD_PICK(shift); OFFGRAD_PICK(scale); OFFGRAD_PICK(act_scale); OFFGRAD_PICK(n1); OFFGRAD_PICK(n_out);
+    OFFGRAD_PICK(activation); OFFGRAD_PICK(mean_mode);
+#undef OFFGRAD_PICK
+    stage_net<CH>(net, p.n_obs, p.n_act, lds, threadIdx.x);
+    float* t_act = lds + L::NET + kExtra + wave * kStage;      // activations [16][64]
+    float* t_del = t_act + 1024;                                // deltas [16][64]; before them: q [16][8], dy [16][8]
+    const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
+    const int ka = (p.n_act + 3) / 4;
+
+    Grads<NT, true> acc;
+    acc.zero();
+    float db3 = 0.0f, st = 0.0f;
+    const int64_t n_tiles = (p.n_rows + kRowsF32 - 1) / kRowsF32, last = p.n_rows - 1;
+    for (int64_t tile = (int64_t)blockIdx.x * kWaves + wave; tile < n_tiles; tile += (int64_t)gridDim.x * kWaves) {
+#pragma unroll 1
+        for (int blk = 0; blk < kRowsF32 / 16; ++blk) {
+            const int64_t r0 = tile * kRowsF32 + 16 * blk;
+            if (r0 >= p.n_rows) break;                           // uniform: the whole block is past the end
+            const int64_t r = r0 + n16;
+            const bool live = r <= last;
+            const int64_t fr = flat_row(p, r);
+            const float* xr = row_ptr(p.obs, fr, p.n_inner);
+            const float* ar = row_ptr(p.action, fr, p.n_inner);
+            float xin[CH], aop[2], xb[4][NT], asb[4];
+#pragma unroll
+            for (int s = 0; s < CH; ++s) xin[s] = x1_elem<CH>(lds, xr, ar, CH * g + s, p.n_obs, p.n_act, cat);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) aop[j] = as_elem<CH>(lds, ar, 4 * j + g, p.n_act);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int64_t fs = flat_row(p, r0 + 4 * s + g);
+                const float* xs = row_ptr(p.obs, fs, p.n_inner);
+                const float* as = row_ptr(p.action, fs, p.n_inner);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) xb[s][nt] = x1_elem<CH>(lds, xs, as, 16 * nt + n16, p.n_obs, p.n_act, cat);
+                asb[s] = as_elem<CH>(lds, as, n16, p.n_act);
+            }
+            V4 h1[4], h2[4], o;
+            forward_block<CH>(lds, xin, aop, ka, net.activation, n16, g, h1, h2, o);
+            // ---- q of the row to its four lanes; each of them forms the row's head (identically)
+            if (g == 0) t_del[n16 * 8] = o[0];
+            atacom::wave_lds_fence();
+            const float q = t_del[n16 * 8];
+            const float d = q - p.target[(r < last ? r : last) * p.target_stride];
+            const float dy = live ? 2.0f * d : 0.0f;
+            db3 += dy;
+            st += live ? d * d : 0.0f;
+            *reinterpret_cast<V4*>(t_del + 128 + n16 * 8) = V4{dy, 0.0f, 0.0f, 0.0f};
+            *reinterpret_cast<V4*>(t_del + 128 + n16 * 8 + 4) = V4{0.0f, 0.0f, 0.0f, 0.0f};
+            backward_block<CH, NT, true>(lds, t_act, t_del, h1, h2, xb, asb, net.activation, n16, g, acc);
+        }
+    }
+    sum_biases(acc);
+    db3 = sum16(db3);
+    st = sum16(st);
+    static_assert((Grads<NT, true>::kSlots + 2) * 64 <= kLds, "the hand-over fits the workgroup's LDS");
+    hand_over(acc, lds, wave, lane, [&](auto&& f, int q) {
+        db3 = f(q++, db3);
+        st = f(q++, st);
+    });
+    if (wave != 0) return;
+    const int64_t Q = partial_size(net.n1, 1, p.n_act);
+    float* out = p.workspace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Q;
+    store_net(acc, out, net.n1, 1, p.n_act, n16, g);
+    if (lane == 0) {
+        const Offsets o = offsets(net.n1, 1, p.n_act);
+        out[o.b3] = db3;
+        out[o.end] = st;
+        out[o.end + 1] = out[o.end + 2] = out[o.end + 3] = 0.0f;
+    }
+}
+
+template <int CH>
+__device__ __forceinline__ void actor_f32(const ActorParams<float>& p) {
+    constexpr int NT = 4 * CH > 16 ? 2 : 1;
+    using L = LdsM<CH>;
+    constexpr int kLds = L::NET + kExtra + kWaves * kStage;
+    __shared__ __attribute__((aligned(16))) float lds[kLds];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n16 = lane & 15, g = lane >> 4;
+    float* stage = lds + L::NET + kExtra + wave * kStage;      // phases A, B: [64][8] outputs / as, then [64][8] dq/das
+    float* t_act = stage;                                       // phase C: the transposition buffers
+    float* t_del = stage + 1024;
+    const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
+    const int ka = (p.n_act + 3) / 4;
+    const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    Grads<NT, false> acc;
+    acc.zero();
+    float db3[NK], st = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) db3[k] = 0.0f;
+    const float noa[2] = {0.0f, 0.0f}, nob[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int64_t n_tiles = (p.n_rows + kRowsF32 - 1) / kRowsF32, step = (int64_t)gridDim.x * kWaves, last = p.n_rows - 1;
+    const int64_t rounds = (n_tiles + step - 1) / step;         // uniform per workgroup: every wavefront reaches every barrier
+    stage_net<CH>(p.actor, p.n_obs, p.n_act, lds, threadIdx.x);
+    for (int64_t round = 0; round < rounds; ++round) {
+        const int64_t base = (round * step + (int64_t)blockIdx.x * kWaves + wave) * kRowsF32;
+        const int64_t ro = base + lane;                          // the row this lane owns between the phases
+        const bool live_o = ro <= last;
+        // ---- phase A: the actor's outputs m of the tile -> [64][8], then a and d a / d m at the owners
+#pragma unroll 1
+        for (int blk = 0; blk < 4; ++blk) {
+            const int64_t r0 = base + 16 * blk;
+            if (r0 >= p.n_rows) break;
+            const float* xr = row_ptr(p.obs, flat_row(p, r0 + n16), p.n_inner);
+            float xin[CH];
+#pragma unroll
+            for (int s = 0; s < CH; ++s) xin[s] = obs_elem<CH>(lds, xr, CH * g + s, p.n_obs);
+            V4 h1[4], h2[4], o;
+            forward_block<CH>(lds, xin, noa, 0, p.actor.activation, n16, g, h1, h2, o);
+            if (g < 2) *reinterpret_cast<V4*>(stage + (16 * blk + n16) * 8 + 4 * g) = o;
+        }
+        atacom::wave_lds_fence();
+        float a[NK], gm[NK];
+        {
+            const V4 m0 = *reinterpret_cast<const V4*>(stage + lane * 8), m1 = *reinterpret_cast<const V4*>(stage + lane * 8 + 4);
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const float m = k < 4 ? m0[k & 3] : m1[k & 3];
+                a[k] = 0.0f;
+                gm[k] = 0.0f;
+                if (k < p.n_act && live_o) {
+                    if (p.actor.mean_mode) {
+                        const float s = lds[L::AUX + k], t = atacom::num<float>::tanh(m);
+                        a[k] = s * t;
+                        gm[k] = s * __builtin_fmaf(-t, t, 1.0f);
+                    } else {
+                        a[k] = m;
+                        gm[k] = 1.0f;
+                    }
+                }
+            }
+        }
+        atacom::wave_lds_fence();
+        if (p.aout && live_o) {
+            float* ao = p.aout + ro * p.aout_stride;
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+                if (k < p.n_act) ao[k] = a[k];
+        }
+        // ---- phase B: the critic on (obs, a) and its input gradient -> [64][8] behind the rows' as
+        stage_net<CH>(p.critic, p.n_obs, p.n_act, lds, threadIdx.x);
+        {
+            float as[NK];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) as[k] = k < p.n_act ? a[k] / lds[L::AUX + k] : 0.0f;
+            *reinterpret_cast<V4*>(stage + lane * 8) = V4{as[0], as[1], as[2], as[3]};
+            *reinterpret_cast<V4*>(stage + lane * 8 + 4) = V4{as[4], as[5], as[6], as[7]};
+        }
+        atacom::wave_lds_fence();
+#pragma unroll 1
+        for (int blk = 0; blk < 4; ++blk) {
+            const int64_t r0 = base + 16 * blk;
+            if (r0 >= p.n_rows) break;
+            const bool live = r0 + n16 <= last;
+            const float* xr = row_ptr(p.obs, flat_row(p, r0 + n16), p.n_inner);
+            const float* asr = stage + (16 * blk + n16) * 8;
+            float xin[CH], aop[2];
+#pragma unroll
+            for (int s = 0; s < CH; ++s) {
+                const int e = CH * g + s, k = e - p.n_obs;
+                const float x = obs_elem<CH>(lds, xr, e, p.n_obs), av = asr[k < 0 ? 0 : (k < NK ? k : NK - 1)];
+                xin[s] = e < p.n_obs ? x : ((cat && k < p.n_act) ? av : 0.0f);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) aop[j] = asr[4 * j + g];
+            V4 h1[4], h2[4], o;
+            forward_block<CH>(lds, xin, aop, ka, p.critic.activation, n16, g, h1, h2, o);
+            st += (live && g == 0) ? -o[0] : 0.0f;
+            // delta2 = W3^T * act'(h2) from dq = 1
+            V4 d2[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) d2[u] = *reinterpret_cast<const V4*>(lds + L::W3 + 16 * u + 4 * g);
+            times_act_prime(d2, h2, p.critic.activation);
+            // dq/das[k] = sum_j W2a[j][k] delta2[j]: M = k (n16 < 8), N = row n16, K-step (u, v) = unit 16 u + 4 g + v
+            V4 gq = zero;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    gq = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[L::W2A + (16 * u + 4 * g + v) * 8 + (n16 & 7)], d2[u][v], gq, 0, 0, 0);
+            if (cat) {                                           // wave-uniform: + sum_j W1[j][D + k] delta1[j]
+                V4 d1[4] = {zero, zero, zero, zero};
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const float* wrow = lds + L::W2 + (16 * u + 4 * g + v) * L::S2 + n16;
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) d1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[16 * t], d2[u][v], d1[t], 0, 0, 0);
+                    }
+                times_act_prime(d1, h1, p.critic.activation);
+                const int kk = (n16 & 7) < p.n_act ? (n16 & 7) : p.n_act - 1, e = p.n_obs + kk;   // the rows k >= n_act are not stored
+                const int slot = (e / CH) * 8 + e % CH;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v)
+                        gq = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[L::W1 + (16 * t + 4 * g + v) * L::S1 + slot], d1[t][v], gq, 0, 0, 0);
+            }
+            if (g < 2) *reinterpret_cast<V4*>(stage + 512 + (16 * blk + n16) * 8 + 4 * g) = gq;
+        }
+        atacom::wave_lds_fence();
+        float dm[NK];
+        {
+            const V4 g0 = *reinterpret_cast<const V4*>(stage + 512 + lane * 8), g1 = *reinterpret_cast<const V4*>(stage + 512 + lane * 8 + 4);
+            float dq[NK];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const float gs = k < 4 ? g0[k & 3] : g1[k & 3];
+                dq[k] = (k < p.n_act && live_o) ? gs / lds[L::AUX + k] : 0.0f;
+                dm[k] = (k < p.n_act && live_o) ? -(dq[k] * gm[k]) : 0.0f;
+                db3[k] += dm[k];
+            }
+            if (p.dqout && live_o) {
+                float* dqo = p.dqout + ro * p.dqout_stride;
+#pragma unroll
+                for (int k = 0; k < NK; ++k)
+                    if (k < p.n_act) dqo[k] = dq[k];
+            }
+        }
+        atacom::wave_lds_fence();
+        // ---- phase C: the actor again, forward (its activations are recomputed, not kept) and backward from dm
+        stage_net<CH>(p.actor, p.n_obs, p.n_act, lds, threadIdx.x);
+#pragma unroll 1
+        for (int blk = 0; blk < 4; ++blk) {
+            const int64_t r0 = base + 16 * blk;
+            if (r0 >= p.n_rows) break;
+            if (g == blk) {                                      // the owners of the block's rows: dy [16][8]
+                *reinterpret_cast<V4*>(t_del + 128 + n16 * 8) = V4{dm[0], dm[1], dm[2], dm[3]};
+                *reinterpret_cast<V4*>(t_del + 128 + n16 * 8 + 4) = V4{dm[4], dm[5], dm[6], dm[7]};
+            }
+            const float* xr = row_ptr(p.obs, flat_row(p, r0 + n16), p.n_inner);
+            float xin[CH], xb[4][NT];
+#pragma unroll
+            for (int s = 0; s < CH; ++s) xin[s] = obs_elem<CH>(lds, xr, CH * g + s, p.n_obs);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const float* xs = row_ptr(p.obs, flat_row(p, r0 + 4 * s + g), p.n_inner);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) xb[s][nt] = obs_elem<CH>(lds, xs, 16 * nt + n16, p.n_obs);
+            }
+            V4 h1[4], h2[4], o;
+            forward_block<CH>(lds, xin, noa, 0, p.actor.activation, n16, g, h1, h2, o);
+            backward_block<CH, NT, false>(lds, t_act, t_del, h1, h2, xb, nob, p.actor.activation, n16, g, acc);
+        }
+    }
+    sum_biases(acc);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) db3[k] = sum64(db3[k]);
+    st = sum16(st);
+    static_assert((Grads<NT, false>::kSlots + NK + 1) * 64 <= kLds, "the hand-over fits the workgroup's LDS");
+    hand_over(acc, lds, wave, lane, [&](auto&& f, int q) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) db3[k] = f(q++, db3[k]);
+        st = f(q++, st);
+    });
+    if (wave != 0) return;
+    const int64_t Q = partial_size(p.n_obs, p.n_act, 0);
+    float* out = p.workspace + (int64_t)blockIdx.x * Q;
+    store_net(acc, out, p.n_obs, p.n_act, 0, n16, g);
+    if (lane == 0) {
+        const Offsets o = offsets(p.n_obs, p.n_act, 0);
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            if (k < p.n_act) out[o.b3 + k] = db3[k];
+        out[o.end] = st;
+        out[o.end + 1] = out[o.end + 2] = out[o.end + 3] = 0.0f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ float64
+// A workgroup takes 16 rows at a time, sixteen threads a row; the weights are read from memory, the rows' activations and
+// deltas lie in LDS as one record per row, and every thread owns the entries tid, tid + 256, ... of the partial, each the sum
+// over rows of the product of two columns of the records.
+__device__ __forceinline__ double act_prime(double h, int activation) {
+    return activation == 0 ? (h > 0.0 ? 1.0 : 0.0) : __builtin_fma(-h, h, 1.0);
+}
+
+// columns of a record: the network whose gradient is taken (h1 | h2 | delta1 | delta2 | its first-layer input | as | dy), the
+// statistic, 1 and 0; the actor kernel appends its critic's columns
+struct Rec {
+    static constexpr int H1 = 0, H2 = H1 + H, D1 = H2 + H, D2 = D1 + H, X = D2 + H, AS = X + 32, DY = AS + NK, ST = DY + NK,
+                         ONE = ST + 1, ZERO = ONE + 1, SIZE = ZERO + 1;
+};
+
+struct RecActor : Rec {
+    static constexpr int CH1 = Rec::SIZE, CH2 = CH1 + H, CX = CH2 + H, GM = CX + 32, SIZE = GM + NK;
+};
+
+// the two columns whose product, summed over the rows, is entry e of the partial; past its end: 0 * 1
+__device__ __forceinline__ void entry_columns(int e, int n_in, int n_out, int n_act, const Offsets& o, int& ca, int& cb) {
+    ca = Rec::ZERO;
+    cb = Rec::ONE;
+    if (e < o.b1) { ca = Rec::D1 + e / n_in; cb = Rec::X + e % n_in; }
+    else if (e < o.W2) ca = Rec::D1 + (e - o.b1);
+    else if (e < o.b2) { ca = Rec::D2 + (e - o.W2) / H; cb = Rec::H1 + (e - o.W2) % H; }
+    else if (e < o.W3) ca = Rec::D2 + (e - o.b2);
+    else if (e < o.b3) { ca = Rec::DY + (e - o.W3) / H; cb = Rec::H2 + (e - o.W3) % H; }
+    else if (e < o.W2a) ca = Rec::DY + (e - o.b3);
+    else if (e < o.end) { ca = Rec::D2 + (e - o.W2a) / n_act; cb = Rec::AS + (e - o.W2a) % n_act; }
+    else if (e == o.end) ca = Rec::ST;
+}
+
+constexpr int kMaxQ = H * 32 + H + H * H + H + H * NK + NK + H * NK + kStats, kNQ = (kMaxQ + kBlock - 1) / kBlock;
+
+// two hidden layers of a network from the columns cx (n_in values) and, with W2a, AS, into the columns ch1, ch2
+__device__ __forceinline__ void hidden_f64(const Net<double>& n, double* me, int cx, int ch1, int ch2, int n_act, bool live, int c) {
+    if (live)
+        for (int j = c; j < H; j += 16) {
+            double a = n.b1[j];
+            for (int e = 0; e < n.n1; ++e) a = __builtin_fma(n.W1[j * n.n1 + e], me[cx + e], a);
+            me[ch1 + j] = atacom::mlp_act(a, n.activation);
+        }
+    __syncthreads();
+    if (live)
+        for (int j = c; j < H; j += 16) {
+            double a = n.b2[j];
+            for (int i = 0; i < H; ++i) a = __builtin_fma(n.W2[j * H + i], me[ch1 + i], a);
+            if (n.W2a)
+                for (int k = 0; k < n_act; ++k) a = __builtin_fma(n.W2a[j * n_act + k], me[Rec::AS + k], a);
+            me[ch2 + j] = atacom::mlp_act(a, n.activation);
+        }
+    __syncthreads();
+}
+
+// delta2 and delta1 of the thread's row from its dy, h2 and h1
+__device__ __forceinline__ void backward_f64(const Net<double>& n, double* me, bool live, int c) {
+    if (live)
+        for (int j = c; j < H; j += 16) {
+            double a = 0.0;
+            for (int k = 0; k < n.n_out; ++k) a = __builtin_fma(n.W3[k * H + j], me[Rec::DY + k], a);
+            me[Rec::D2 + j] = a * act_prime(me[Rec::H2 + j], n.activation);
+        }
+    __syncthreads();
+    if (live)
+        for (int i = c; i < H; i += 16) {
+            double a = 0.0;
+            for (int j = 0; j < H; ++j) a = __builtin_fma(n.W2[j * H + i], me[Rec::D2 + j], a);
+            me[Rec::D1 + i] = a * act_prime(me[Rec::H1 + i], n.activation);
+        }
+    __syncthreads();
+}
+
+template <int SIZE>
+__device__ __forceinline__ void accumulate_f64(const double* rec, int rows, const int (&ca)[kNQ], const int (&cb)[kNQ], double (&acc)[kNQ]) {
+#pragma unroll
+    for (int q = 0; q < kNQ; ++q)
+        for (int rr = 0; rr < rows; ++rr) acc[q] = __builtin_fma(rec[rr * SIZE + ca[q]], rec[rr * SIZE + cb[q]], acc[q]);
+    __syncthreads();
+}
+
+__device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
+    constexpr int R = kRowsF64;
+    using C = Rec;
+    __shared__ double rec[R * C::SIZE];
+    const int tid = threadIdx.x, row = tid >> 4, c = tid & 15;
+    Net<double> net;
+    const bool second = blockIdx.y != 0;
+#define OFFGRAD_PICK(f) net.f = second ? p.net[1].f : p.net[0].f
+    OFFGRAD_PICK(W1); OFFGRAD_PICK(b1); OFFGRAD_PICK(W2); OFFGRAD_PICK(b2); OFFGRAD_PICK(W2a); OFFGRAD_PICK(W3); OFFGRAD_PICK(b3);
+    OFFGRAD_PICK(shift); OFFGRAD_PICK(scale); OFFGRAD_PICK(act_scale); OFFGRAD_PICK(n1); OFFGRAD_PICK(n_out);
+    OFFGRAD_PICK(activation); OFFGRAD_PICK(mean_mode);
+#undef OFFGRAD_PICK
+    const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
+    const int Q = (int)partial_size(net.n1, 1, p.n_act);
+    const Offsets o = offsets(net.n1, 1, p.n_act);
+    int ca[kNQ], cb[kNQ];
+    double acc[kNQ];
+#pragma unroll
+    for (int q = 0; q < kNQ; ++q) {
+        acc[q] = 0.0;
+        entry_columns(tid + kBlock * q, net.n1, 1, p.n_act, o, ca[q], cb[q]);
+    }
+    const int64_t n_tiles = (p.n_rows + R - 1) / R;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t r = tile * R + row;
+        const bool live = r < p.n_rows;
+        const int64_t left = p.n_rows - tile * R;
+        const int rows = left < R ? (int)left : R;
+        const int64_t fr = flat_row(p, r);
+        double* me = rec + row * C::SIZE;
+        if (live) {
+            const double* xr = row_ptr(p.obs, fr, p.n_inner);
+            const double* ar = row_ptr(p.action, fr, p.n_inner);
+            for (int e = c; e < p.n_obs; e += 16) me[C::X + e] = (xr[e] - (net.shift ? net.shift[e] : 0.0)) * (net.scale ? net.scale[e] : 1.0);
+            if (c < NK) {
+                const double as = c < p.n_act ? ar[c] / (net.act_scale ? net.act_scale[c] : 1.0) : 0.0;
+                me[C::AS + c] = as;
+                if (cat && c < p.n_act) me[C::X + p.n_obs + c] = as;
+                me[C::DY + c] = 0.0;
+            }
+            if (c == 0) { me[C::ONE] = 1.0; me[C::ZERO] = 0.0; }
+        }
+        __syncthreads();
+        hidden_f64(net, me, C::X, C::H1, C::H2, p.n_act, live, c);
+        if (live && c == 0) {
+            double q = net.b3[0];
+            for (int j = 0; j < H; ++j) q = __builtin_fma(net.W3[j], me[C::H2 + j], q);
+            const double d = q - p.target[r * p.target_stride];
+            me[C::DY] = 2.0 * d;
+            me[C::ST] = d * d;
+        }
+        __syncthreads();
+        backward_f64(net, me, live, c);
+        accumulate_f64<C::SIZE>(rec, rows, ca, cb, acc);
+    }
+    double* out = p.workspace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Q;
+#pragma unroll
+    for (int q = 0; q < kNQ; ++q)
+        if (tid + kBlock * q < Q) out[tid + kBlock * q] = acc[q];
+}
+
+__device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
+    constexpr int R = kRowsF64;
+    using C = RecActor;
+    __shared__ double rec[R * C::SIZE];
+    const int tid = threadIdx.x, row = tid >> 4, c = tid & 15;
+    const Net<double>& A = p.actor;
+    const Net<double>& Qn = p.critic;
+    const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
+    const int k = p.n_act, D = p.n_obs;
+    const int Q = (int)partial_size(D, k, 0);
+    const Offsets o = offsets(D, k, 0);
+    int ca[kNQ], cb[kNQ];
+    double acc[kNQ];
+#pragma unroll
+    for (int q = 0; q < kNQ; ++q) {
+        acc[q] = 0.0;
+        entry_columns(tid + kBlock * q, D, k, 0, o, ca[q], cb[q]);
+    }
+    const int64_t n_tiles = (p.n_rows + R - 1) / R;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t r = tile * R + row;
+        const bool live = r < p.n_rows;
+        const int64_t left = p.n_rows - tile * R;
+        const int rows = left < R ? (int)left : R;
+        const int64_t fr = flat_row(p, r);
+        double* me = rec + row * C::SIZE;
+        if (live) {
+            const double* xr = row_ptr(p.obs, fr, p.n_inner);
+            for (int e = c; e < D; e += 16) {
+                me[C::X + e] = (xr[e] - (A.shift ? A.shift[e] : 0.0)) * (A.scale ? A.scale[e] : 1.0);
+                me[C::CX + e] = (xr[e] - (Qn.shift ? Qn.shift[e] : 0.0)) * (Qn.scale ? Qn.scale[e] : 1.0);
+            }
+            if (c == 0) { me[C::ONE] = 1.0; me[C::ZERO] = 0.0; }
+        }
+        __syncthreads();
+        hidden_f64(A, me, C::X, C::H1, C::H2, 0, live, c);
+        if (live && c < NK) {
+            double a = 0.0, gm = 0.0;
+            if (c < k) {
+                double m = A.b3[c];
+                for (int j = 0; j < H; ++j) m = __builtin_fma(A.W3[c * H + j], me[C::H2 + j], m);
+                if (A.mean_mode) {
+                    const double s = A.act_scale ? A.act_scale[c] : 1.0, t = ::tanh(m);
+                    a = s * t;
+                    gm = s * __builtin_fma(-t, t, 1.0);
+                } else {
+                    a = m;
+                    gm = 1.0;
+                }
+                if (p.aout) p.aout[r * p.aout_stride + c] = a;
+            }
+            const double as = c < k ? a / (Qn.act_scale ? Qn.act_scale[c] : 1.0) : 0.0;
+            me[C::AS + c] = as;
+            me[C::GM + c] = gm;
+            if (cat && c < k) me[C::CX + D + c] = as;
+        }
+        __syncthreads();
+        hidden_f64(Qn, me, C::CX, C::CH1, C::CH2, k, live, c);
+        if (live && c == 0) {
+            double q = Qn.b3[0];
+            for (int j = 0; j < H; ++j) q = __builtin_fma(Qn.W3[j], me[C::CH2 + j], q);
+            me[C::ST] = -q;
+        }
+        __syncthreads();
+        if (live)                                                // delta2 of the critic over its h2, in place
+            for (int j = c; j < H; j += 16) me[C::CH2 + j] = Qn.W3[j] * act_prime(me[C::CH2 + j], Qn.activation);
+        __syncthreads();
+        if (live && cat)                                         // delta1 over h1, in place: thread c owns its units
+            for (int i = c; i < H; i += 16) {
+                double a = 0.0;
+                for (int j = 0; j < H; ++j) a = __builtin_fma(Qn.W2[j * H + i], me[C::CH2 + j], a);
+                me[C::CH1 + i] = a * act_prime(me[C::CH1 + i], Qn.activation);
+            }
+        __syncthreads();
+        if (live && c < NK) {
+            double dm = 0.0;
+            if (c < k) {
+                double gs = 0.0;
+                for (int j = 0; j < H; ++j) gs = __builtin_fma(Qn.W2a[j * k + c], me[C::CH2 + j], gs);
+                if (cat)
+                    for (int j = 0; j < H; ++j) gs = __builtin_fma(Qn.W1[j * Qn.n1 + D + c], me[C::CH1 + j], gs);
+                const double dq = gs / (Qn.act_scale ? Qn.act_scale[c] : 1.0);
+                if (p.dqout) p.dqout[r * p.dqout_stride + c] = dq;
+                dm = -(dq * me[C::GM + c]);
+            }
+            me[C::DY + c] = dm;
+        }
+        __syncthreads();
+        backward_f64(A, me, live, c);
+        accumulate_f64<C::SIZE>(rec, rows, ca, cb, acc);
+    }
+    double* out = p.workspace + (int64_t)blockIdx.x * Q;
+#pragma unroll
+    for (int q = 0; q < kNQ; ++q)
+        if (tid + kBlock * q < Q) out[tid + kBlock * q] = acc[q];
+}
+
+// one wavefront per SIMD: the float32 kernels keep up to 160 accumulator registers next to their operands
+template <typename T, int CH>
+__global__ __launch_bounds__(kBlock, 1) void k_offgrad_critic(const CriticParams<T> p) {
+    if constexpr (std::is_same<T, float>::value) critic_f32<CH>(p);
+    else critic_f64(p);
+}
+
+template <typename T, int CH>
+__global__ __launch_bounds__(kBlock, 1) void k_offgrad_actor(const ActorParams<T> p) {
+    if constexpr (std::is_same<T, float>::value) actor_f32<CH>(p);
+    else actor_f64(p);
+}
+
+// grad and stats of network blockIdx.y from its partials: a workgroup takes kReduceValues consecutive values; slice s of its
+// threads adds the partials s, s + kReduceSlices, ... in that order, the slices' sums are added in the order of s, and the sum
+// is divided by the number of rows
+template <typename T>
+struct ReduceParams {
+    const T* ws;
+    T* grad[2];
+    T* stats[2];
+    int blocks, q_size;
+    T m;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kReduceBlock) void k_offgrad_reduce(const ReduceParams<T> p) {
+    __shared__ T part[kReduceSlices][kReduceValues];
+    const int v = threadIdx.x % kReduceValues, slice = threadIdx.x / kReduceValues;
+    const int i = blockIdx.x * kReduceValues + v;
+    const T* ws = p.ws + (int64_t)blockIdx.y * p.blocks * p.q_size;
+    T s = T(0);
+    if (i < p.q_size)
+        for (int b = slice; b < p.blocks; b += kReduceSlices) s += ws[(int64_t)b * p.q_size + i];
+    part[slice][v] = s;
+    __syncthreads();
+    if (slice != 0 || i >= p.q_size) return;
+#pragma unroll
+    for (int k = 1; k < kReduceSlices; ++k) s += part[k][v];
+    s = s / p.m;
+    T* grad = blockIdx.y ? p.grad[1] : p.grad[0];
+    T* stats = blockIdx.y ? p.stats[1] : p.stats[0];
+    const int n_grad = p.q_size - kStats;
+    if (i < n_grad) grad[i] = s;
+    else stats[i - n_grad] = s;
+}
+
+namespace {
+
+template <typename T>
+Net<T> net_of(const NetDesc& d) {
+    return Net<T>{(const T*)d.W1, (const T*)d.b1, (const T*)d.W2, (const T*)d.b2, (const T*)d.W2a, (const T*)d.W3, (const T*)d.b3,
+                  (const T*)d.shift, (const T*)d.scale, (const T*)d.act_scale, d.n1, d.n_out, d.activation, d.mean_mode};
+}
+
+template <typename T>
+Rows<T> rows_of(const RowView& v) {
+    return Rows<T>{(const T*)v.ptr, v.so, v.si};
+}
+
+template <typename T>
+void reduce(const void* ws, void* const (&grad)[2], void* const (&stats)[2], int n_nets, int blocks, int q, int64_t rows, hipStream_t s) {
+    ReduceParams<T> r{(const T*)ws, {(T*)grad[0], (T*)grad[1]}, {(T*)stats[0], (T*)stats[1]}, blocks, q, (T)rows};
+    hipLaunchKernelGGL((k_offgrad_reduce<T>), dim3((q + kReduceValues - 1) / kReduceValues, n_nets), dim3(kReduceBlock), 0, s, r);
+}
+
+#define OFFGRAD_GO(KERNEL, GRID, CH) \
+    case CH: hipLaunchKernelGGL((KERNEL<T, CH>), GRID, dim3(kBlock), 0, s, p); break
+#define OFFGRAD_SWITCH(KERNEL, GRID, n1)                                                                                  \
+    switch (((n1) + 3) / 4) {                                                                                             \
+        OFFGRAD_GO(KERNEL, GRID, 1); OFFGRAD_GO(KERNEL, GRID, 2); OFFGRAD_GO(KERNEL, GRID, 3); OFFGRAD_GO(KERNEL, GRID, 4); \
+        OFFGRAD_GO(KERNEL, GRID, 5); OFFGRAD_GO(KERNEL, GRID, 6); OFFGRAD_GO(KERNEL, GRID, 7); OFFGRAD_GO(KERNEL, GRID, 8); \
+        default: return ATACOM_OFFGRAD_E_UNSUPPORTED;                                                                     \
+    }
+
+template <typename T>
+int launch_critic(const CriticCall& c, int blocks, hipStream_t s) {
+    CriticParams<T> p{};
+    for (int n = 0; n < c.n_nets; ++n) p.net[n] = net_of<T>(c.net[n]);
+    if (c.n_nets == 1) p.net[1] = p.net[0];
+    p.kind = c.kind; p.n_obs = c.n_obs; p.n_act = c.n_act; p.n_rows = c.n_rows; p.n_inner = c.n_inner; p.idx = c.idx;
+    p.obs = rows_of<T>(c.obs); p.action = rows_of<T>(c.action);
+    p.target = (const T*)c.target; p.target_stride = c.target_stride; p.workspace = (T*)c.workspace;
+    const int n1 = c.net[0].n1;
+    OFFGRAD_SWITCH(k_offgrad_critic, dim3(blocks, c.n_nets), n1)
+    reduce<T>(c.workspace, c.grad, c.stats, c.n_nets, blocks, (int)partial_size(n1, 1, c.n_act), c.n_rows, s);
+    return ATACOM_OFFGRAD_OK;
+}
+
+template <typename T>
+int launch_actor(const ActorCall& c, int blocks, hipStream_t s) {
+    ActorParams<T> p{};
+    p.actor = net_of<T>(c.actor); p.critic = net_of<T>(c.critic);
+    p.kind = c.kind; p.n_obs = c.n_obs; p.n_act = c.n_act; p.n_rows = c.n_rows; p.n_inner = c.n_inner; p.idx = c.idx;
+    p.obs = rows_of<T>(c.obs);
+    p.aout = (T*)c.action_out; p.aout_stride = c.action_out_stride; p.dqout = (T*)c.dqda_out; p.dqout_stride = c.dqda_out_stride;
+    p.workspace = (T*)c.workspace;
+    OFFGRAD_SWITCH(k_offgrad_actor, dim3(blocks), c.critic.n1)   // the critic's first layer: the widest of the call
+    void* const grad[2] = {c.grad, c.grad};
+    void* const stats[2] = {c.stats, c.stats};
+    reduce<T>(c.workspace, grad, stats, 1, blocks, (int)partial_size(c.n_obs, c.n_act, 0), c.n_rows, s);
+    return ATACOM_OFFGRAD_OK;
+}
+
+#undef OFFGRAD_SWITCH
+#undef OFFGRAD_GO
+
+}  // namespace
+
+int critic_launch(const CriticCall& c, int blocks, hipStream_t s) {
+    if (c.dtype == ATACOM_OFFGRAD_F32) return launch_critic<float>(c, blocks, s);
+    if (c.dtype == ATACOM_OFFGRAD_F64) return launch_critic<double>(c, blocks, s);
+    return ATACOM_OFFGRAD_E_UNSUPPORTED;
+}
+
+int actor_launch(const ActorCall& c, int blocks, hipStream_t s) {
+    if (c.dtype == ATACOM_OFFGRAD_F32) return launch_actor<float>(c, blocks, s);
+    if (c.dtype == ATACOM_OFFGRAD_F64) return launch_actor<double>(c, blocks, s);
+    return ATACOM_OFFGRAD_E_UNSUPPORTED;
+}
+
+}  // namespace atacom_offgrad

@@ -2,7 +2,7 @@
 (include/atacom_offpolicy_hip.h states the arithmetic): a replay memory in the project's record format, the Q-value of the
 reference's two-branch critic, the fused TD target  r + gamma (1 - absorbing) min_j Q'_j(s', clip(pi'(s') + clip(sigma eps)))
 of a minibatch gathered through row numbers from the memory in place, and MushroomRL's soft target update, one launch each.
-The critic and actor gradients are not here: the losses stay with torch autograd (examples/td3_air_hockey.py).
+The critic and actor gradients are the other half, offgrad.py (libatacom_offgrad.so); ReplayMemory forwards to both.
 
 Every call is enqueued on the current stream of the tensors' device and nothing synchronises.  With `out=` (and parameters
 that already live on the device in the call's dtype) a call allocates nothing and can be captured in a graph.  Forward passes
@@ -383,3 +383,15 @@ class ReplayMemory:
         """td_target on the next_obs, reward and absorbing columns of the storage, in place."""
         c = record_columns(self.storage, self.fields)
         return td_target(actor, critics, c['next_obs'], c['reward'], c['absorbing'], gamma, idx=idx, **kw)
+
+    def critic_gradient(self, critics, idx, target, **kw):
+        """offgrad.critic_gradient on the obs and action columns of the storage, in place; target [M] is row r of the call."""
+        from .offgrad import critic_gradient
+        c = record_columns(self.storage, self.fields)
+        return critic_gradient(critics, c['obs'], c['action'], target, idx=idx, **kw)
+
+    def actor_gradient(self, actor, critic, idx, **kw):
+        """offgrad.actor_gradient on the obs column of the storage, in place."""
+        from .offgrad import actor_gradient
+        c = record_columns(self.storage, self.fields)
+        return actor_gradient(actor, critic, c['obs'], idx=idx, **kw)
