@@ -20,7 +20,8 @@ may be appended (EXTENSIONS is pinned at its one row too).  It holds libatacom_o
 include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fisher-vector product of a TRPO policy step,
 include/atacom_trust_hip.h), the tenth, and libatacom_offpolicy.so (the critic's Q-value, the fused TD target and the soft target
 update of DDPG and TD3, include/atacom_offpolicy_hip.h), the eleventh, and libatacom_offgrad.so (the critic and actor gradients of a
-DDPG / TD3 update, include/atacom_offgrad_hip.h), the twelfth; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
+DDPG / TD3 update, include/atacom_offgrad_hip.h), the twelfth, and libatacom_soft.so (the soft TD target, the critic and actor
+gradients and the temperature step of a SAC update, include/atacom_soft_hip.h), the thirteenth; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
 it holds the headers that libatacom_fit.so and libatacom_trust.so share, which sources() finds through their #include lines.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
@@ -52,12 +53,14 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 # atacom_returns.hip: the fused multiply-adds of its recurrences are the explicit ones (include/atacom_returns_hip.h); the compiler
 # adds none.  atacom_optim.hip: every operation of the Adam step is the individually rounded one its header writes; so are the
 # target arithmetic and the soft update of atacom_offpolicy.hip (the fused multiply-adds of its float64 networks are explicit) and
-# the row arithmetic of atacom_offgrad.hip (squash, its derivative, the division by act_scale, the head)
+# the row arithmetic of atacom_offgrad.hip (squash, its derivative, the division by act_scale, the head) and of atacom_soft.hip
+# (the squashed Gaussian's sample, its log-probability and their derivatives, the target, the temperature's Adam step)
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
               'atacom_returns.hip': ['-ffp-contract=off'],
               'atacom_optim.hip': ['-ffp-contract=off'],
               'atacom_offpolicy.hip': ['-ffp-contract=off'],
-              'atacom_offgrad.hip': ['-ffp-contract=off']}
+              'atacom_offgrad.hip': ['-ffp-contract=off'],
+              'atacom_soft.hip': ['-ffp-contract=off']}
 
 # One row per library, keyed by its name: the units it compiles and `tuning`, whether it takes the ATACOM_ONLY_UNITS /
 # kept-object path below.  Everything else follows from the key (_binding.naming()).  A new library is a new row here, a
@@ -108,6 +111,7 @@ ADDITIONS = {
     'trust': _target('trust', ['atacom_trust.hip', 'atacom_trust_capi.cpp'], False, sub='trust'),
     'offpolicy': _target('offpolicy', ['atacom_offpolicy.hip', 'atacom_offpolicy_capi.cpp'], False, sub='offpolicy'),
     'offgrad': _target('offgrad', ['atacom_offgrad.hip', 'atacom_offgrad_capi.cpp'], False, sub='offgrad'),
+    'soft': _target('soft', ['atacom_soft.hip', 'atacom_soft_capi.cpp'], False, sub='soft'),
 }
 """The open table: rows of the same kind as TARGETS and EXTENSIONS, and rows MAY BE APPENDED.  TARGETS and EXTENSIONS are
 pinned entry by entry by the tests that guard them; this one is checked row by row (each row's own properties, and that the
@@ -120,7 +124,10 @@ atacom_policy.h, its host description, the host scaffolding and the view type of
 atacom_policy.h, the host description of a network, the host scaffolding and the view type of atacom_evaluate_hip.h, and nothing
 of csrc/mlp/, 'fit', 'trust' or 'optim'.
 'offgrad': the backward half of a DDPG / TD3 update (include/atacom_offgrad_hip.h); it borrows what 'offpolicy' borrows, declares
-its own critic descriptor and carries its own backward pass: nothing of csrc/mlp/, 'fit', 'trust', 'optim' or 'offpolicy'."""
+its own critic descriptor and carries its own backward pass: nothing of csrc/mlp/, 'fit', 'trust', 'optim' or 'offpolicy'.
+'soft': a SAC update (include/atacom_soft_hip.h): the fused soft target, the critics' and the squashed-Gaussian actor's gradients
+and Adam on log_alpha; it borrows what 'offgrad' borrows, declares its own critic descriptor and carries its own backward pass:
+nothing of csrc/mlp/, 'fit', 'trust', 'optim', 'offpolicy' or 'offgrad'."""
 
 
 def _row(name):

@@ -395,3 +395,21 @@ class ReplayMemory:
         from .offgrad import actor_gradient
         c = record_columns(self.storage, self.fields)
         return actor_gradient(actor, critic, c['obs'], idx=idx, **kw)
+
+    def soft_td_target(self, policy, critics, idx, gamma, log_alpha, eps, **kw):
+        """soft.soft_td_target on the next_obs, reward and absorbing columns of the storage, in place."""
+        from .soft import soft_td_target
+        c = record_columns(self.storage, self.fields)
+        return soft_td_target(policy, critics, c['next_obs'], c['reward'], c['absorbing'], gamma, log_alpha, eps, idx=idx, **kw)
+
+    def soft_critic_gradient(self, critics, idx, target, **kw):
+        """soft.soft_critic_gradient on the obs and action columns of the storage, in place; target [M] is row r of the call."""
+        from .soft import soft_critic_gradient
+        c = record_columns(self.storage, self.fields)
+        return soft_critic_gradient(critics, c['obs'], c['action'], target, idx=idx, **kw)
+
+    def soft_actor_gradient(self, policy, critics, idx, eps, log_alpha, target_entropy, **kw):
+        """soft.soft_actor_gradient on the obs column of the storage, in place."""
+        from .soft import soft_actor_gradient
+        c = record_columns(self.storage, self.fields)
+        return soft_actor_gradient(policy, critics, c['obs'], eps, log_alpha, target_entropy, idx=idx, **kw)
