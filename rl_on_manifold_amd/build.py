@@ -21,8 +21,11 @@ include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fish
 include/atacom_trust_hip.h), the tenth, and libatacom_offpolicy.so (the critic's Q-value, the fused TD target and the soft target
 update of DDPG and TD3, include/atacom_offpolicy_hip.h), the eleventh, and libatacom_offgrad.so (the critic and actor gradients of a
 DDPG / TD3 update, include/atacom_offgrad_hip.h), the twelfth, and libatacom_soft.so (the soft TD target, the critic and actor
-gradients and the temperature step of a SAC update, include/atacom_soft_hip.h), the thirteenth; build_additions() builds its rows.  csrc/mlp/ is no library and has no row in any table:
-it holds the headers that libatacom_fit.so and libatacom_trust.so share, which sources() finds through their #include lines.
+gradients and the temperature step of a SAC update, include/atacom_soft_hip.h), the thirteenth; build_additions() builds its rows.
+csrc/mlp/ is no library and has no row in any table: it holds the headers that libatacom_fit.so, libatacom_trust.so,
+libatacom_offgrad.so and libatacom_soft.so share (the backward pass of the 2 x 64 network, atacom_mlp_backward.h; the host checks
+of a call's views, atacom_view_checks.h, which libatacom_offpolicy.so includes too), which sources() finds through their #include
+lines.
 
 The rebuild rule: a library is stale when one of its units, or a file that they reach through `#include "..."` lines, is newer
 than it.  The includes are read from the files themselves (sources()), so there is no list of headers to keep by hand.
@@ -121,13 +124,14 @@ scaffolding by `#include "../..."` and adds no kernel or symbol to the other eig
 'trust': the Fisher-vector product of a trust-region policy step (include/atacom_trust_hip.h); it borrows the network of
 atacom_policy.h, its host description, the host scaffolding and the view type of atacom_evaluate_hip.h, as 'fit' does.
 'offpolicy': the forward half of a DDPG / TD3 update (include/atacom_offpolicy_hip.h); it borrows the LDS layouts of
-atacom_policy.h, the host description of a network, the host scaffolding and the view type of atacom_evaluate_hip.h, and nothing
-of csrc/mlp/, 'fit', 'trust' or 'optim'.
-'offgrad': the backward half of a DDPG / TD3 update (include/atacom_offgrad_hip.h); it borrows what 'offpolicy' borrows, declares
-its own critic descriptor and carries its own backward pass: nothing of csrc/mlp/, 'fit', 'trust', 'optim' or 'offpolicy'.
+atacom_policy.h, the host description of a network, the host scaffolding, the view type of atacom_evaluate_hip.h and the view
+checks of csrc/mlp/ -- nothing else of csrc/mlp/ and nothing of 'fit', 'trust' or 'optim'.
+'offgrad': the backward half of a DDPG / TD3 update (include/atacom_offgrad_hip.h); it borrows what 'offpolicy' borrows and the
+backward pass of csrc/mlp/, which it shares with 'fit', 'trust' and 'soft', and declares its own critic descriptor: nothing of the
+directories of 'fit', 'trust', 'optim' or 'offpolicy'.
 'soft': a SAC update (include/atacom_soft_hip.h): the fused soft target, the critics' and the squashed-Gaussian actor's gradients
-and Adam on log_alpha; it borrows what 'offgrad' borrows, declares its own critic descriptor and carries its own backward pass:
-nothing of csrc/mlp/, 'fit', 'trust', 'optim', 'offpolicy' or 'offgrad'."""
+and Adam on log_alpha; it borrows what 'offgrad' borrows, csrc/mlp/ included, and declares its own critic descriptor: nothing of
+the directories of 'fit', 'trust', 'optim', 'offpolicy' or 'offgrad'."""
 
 
 def _row(name):

@@ -1,8 +1,19 @@
 // The backward pass of the 2 x 64 network of ../atacom_policy.h over the rows of a collection, once: what the kernels of
-// ../fit/atacom_fit.hip (k_fit_gradient) and ../trust/atacom_trust.hip (k_trust_fvp) share, and the constants and sizes their
-// launchers share.  Headers only: csrc/mlp/ is no library, and a unit that includes this file is rebuilt when it changes.  A unit
-// keeps its Params, its forward (and tangent) layers 2 and 3, its head -- what dy is -- and its own tail of the hand-over, of
-// the partial and of the reduction.
+// ../fit/atacom_fit.hip (k_fit_gradient), ../trust/atacom_trust.hip (k_trust_fvp), ../offgrad/atacom_offgrad.hip
+// (k_offgrad_critic, k_offgrad_actor) and ../soft/atacom_soft.hip (k_soft_critic, k_soft_actor) share, and the constants and
+// sizes their launchers share.  Headers only: csrc/mlp/ is no library, and a unit that includes this file is rebuilt when it
+// changes.  A unit keeps its Params, its staging where that differs, its forward (and tangent) layers 2 and 3, its head -- what
+// dy is -- and its own tail of the hand-over, of the partial and of the reduction.
+//
+// THE RULE OF THIS FILE: every expression here means the same with and without floating-point contraction.  Two of the units
+// compile with -ffp-contract=off and two with the compiler's default, and all four must get the same bits from the same grid,
+// so a product followed by an addition is written as an explicit fma (__builtin_fma, __builtin_fmaf, the matrix-core builtin)
+// or the two are kept apart by what lies between them (a subtraction BEFORE a product, a product alone, sums alone).
+//
+// WA: layer 2 of a DDPG / TD3 critic has a second branch, h2 = act(W2 h1 + W2a as + b2) with as the scaled action [n_act <= 8],
+// so its gradient carries dW2a = sum_r delta2_r as_r^T.  Grads, backward, hand_over and store_net take the flag WA (default
+// false: no such branch).  With it dW2a rides on dW2's A operands (one more accumulator, acc2a, handed over between acc2 and
+// acc3) and is stored behind the network's values, at NetOffsets::end; net_columns takes n_act for its float64 column pairs.
 //
 // Float32, one wavefront, one block of 16 rows (lane = (n16, g) = (lane % 16, lane / 16)), on the LDS layout MlpLdsM, the operand
 // mapping of mlp_forward_mfma and the wave-level fence of ../atacom_policy.h:
@@ -12,9 +23,10 @@
 //     lane % 16 = unit, lane / 16 = row: the transposition of the above.  Each goes once through a [16 rows][64 units] buffer of
 //     the wavefront's LDS staging area (put / get; the column is rotated by 16 (row % 4) so that the b128 writes and the b32 reads
 //     are both free of bank conflicts without padding);
-//   * the accumulators (Grads: 16 NT + 64 + 16 registers of dW1, dW2, dW3, NT = 1 or 2 tiles of inputs, and 32 of db1, db2) stay
-//     in registers for the whole walk; at its end the bias sums are added across lanes (sum_biases), wavefronts 1, 2, 3 hand
-//     their registers to wavefront 0 through LDS in that order (hand_over) and wavefront 0 stores the partial (store_net).
+//   * the accumulators (Grads: 16 NT + 64 + 16 registers of dW1, dW2, dW3, NT = 1 or 2 tiles of inputs, 32 of db1, db2 and,
+//     with WA, 16 of dW2a) stay in registers for the whole walk; at its end the bias sums are added across lanes (sum_biases),
+//     wavefronts 1, 2, 3 hand their registers to wavefront 0 through LDS in that order (hand_over) and wavefront 0 stores the
+//     partial (store_net).
 // Float64: one record per row in LDS, sixteen threads a row; every thread owns the entries tid, tid + 256, ... of the partial,
 // each the sum over rows of the product of two columns of the records (net_columns, accumulate_f64).  The record layout is the
 // unit's own (C: columns H1, H2, D1, D2, X, DY, ONE).
@@ -174,17 +186,24 @@ __device__ __forceinline__ float sum16(float v) {      // over the 16 lanes that
     return v;
 }
 
-// a wavefront's accumulators of the network's gradient, for the whole walk
-template <int NT>
+__device__ __forceinline__ float sum64(float v) {      // over the wavefront, in every lane
+    v = sum16(v);
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// a wavefront's accumulators of the network's gradient, for the whole walk; WA: with dW2a (acc2a is dead without it)
+template <int NT, bool WA = false>
 struct Grads {
-    V4 acc1[4][NT], acc2[4][4], acc3[4], db1[4], db2[4];
-    static constexpr int kSlots = 16 * (NT + 7);     // registers of a lane = slots of the hand-over
+    V4 acc1[4][NT], acc2[4][4], acc2a[4], acc3[4], db1[4], db2[4];
+    static constexpr int kSlots = 16 * (NT + 7 + (WA ? 1 : 0));     // registers of a lane = slots of the hand-over
 
     __device__ __forceinline__ void zero() {
         const V4 z = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            acc3[t] = db1[t] = db2[t] = z;
+            acc2a[t] = acc3[t] = db1[t] = db2[t] = z;
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc2[t][u] = z;
 #pragma unroll
@@ -260,11 +279,13 @@ __device__ __forceinline__ void layer1(const float* net, const float (&xin)[CH],
 }
 
 // The backward pass of a block whose dy lies in LDS, [16 rows][8] at t_del + 128 (written by this wavefront, not yet fenced):
-// dW3, da2, dW2, da1, dW1 and the bias gradients into `a`.  `lds` is the staged block of the weights; t_act and t_del are the
-// wavefront's two transposition buffers, free again when it returns.
-template <int CH, int NT>
+// dW3, da2, dW2 (and dW2a), da1, dW1 and the bias gradients into `a`.  `lds` is the staged block of the weights; xb[s][nt] =
+// element 16 nt + n16 of the first layer's input of row 4 s + g of the block and, with WA, asb[s] = as[n16] of that row: the B
+// operands whose K index is the row.  t_act and t_del are the wavefront's two transposition buffers, free again when it returns.
+template <int CH, int NT, bool WA>
 __device__ __forceinline__ void backward(const float* lds, float* t_act, float* t_del, const V4 (&h1)[4], const V4 (&h2)[4],
-                                         const float (&xb)[4][NT], int activation, int n16, int g, Grads<NT>& a) {
+                                         const float (&xb)[4][NT], const float (&asb)[4], int activation, int n16, int g,
+                                         Grads<NT, WA>& a) {
     using L = atacom::MlpLdsM<4 * CH, H, NK>;
     const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
     put(t_act, h2, n16, g);                                  // dW3's B operand; dy is its A operand
@@ -294,16 +315,18 @@ __device__ __forceinline__ void backward(const float* lds, float* t_act, float* 
     put(t_del, da, n16, g);
     put(t_act, h1, n16, g);
     atacom::wave_lds_fence();
-    // ---- dW2[j][i] += sum_rows da2[row][j] h1[row][i]
+    // ---- dW2[j][i] += sum_rows da2[row][j] h1[row][i];  dW2a[j][k] += sum_rows da2[row][j] as[row][k]
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         float x[4], b[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) { x[t] = get(t_del, 4 * s + g, 16 * t + n16); b[t] = get(t_act, 4 * s + g, 16 * t + n16); }
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
+        for (int t = 0; t < 4; ++t) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) a.acc2[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], b[u], a.acc2[t][u], 0, 0, 0);
+            if constexpr (WA) a.acc2a[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], asb[s], a.acc2a[t], 0, 0, 0);
+        }
     }
     // ---- da1 = (W2^T da2) * act'(a1): K-step (u, v) carries unit j = 16 u + 4 g + v, i.e. register v of da[u]
     V4 d1[4] = {zero, zero, zero, zero};
@@ -335,9 +358,17 @@ __device__ __forceinline__ void backward(const float* lds, float* t_act, float* 
     atacom::wave_lds_fence();                            // before the next block writes over the deltas
 }
 
+// ... of a network without the second branch
+template <int CH, int NT>
+__device__ __forceinline__ void backward(const float* lds, float* t_act, float* t_del, const V4 (&h1)[4], const V4 (&h2)[4],
+                                         const float (&xb)[4][NT], int activation, int n16, int g, Grads<NT>& a) {
+    const float none[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    backward<CH, NT, false>(lds, t_act, t_del, h1, h2, xb, none, activation, n16, g, a);
+}
+
 // the wavefront's sums of the bias gradients over the rows (lane % 16)
-template <int NT>
-__device__ __forceinline__ void sum_biases(Grads<NT>& a) {
+template <int NT, bool WA>
+__device__ __forceinline__ void sum_biases(Grads<NT, WA>& a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -345,10 +376,11 @@ __device__ __forceinline__ void sum_biases(Grads<NT>& a) {
 }
 
 // The workgroup's sums: wavefronts 1, 2, 3 hand their registers to wavefront 0 through LDS, in that order.  Every register of
-// every lane is handed over, [slot][lane]: the Grads<NT>::kSlots of `a` first, then the unit's own -- own(f, q) applies
-// x = f(q++, x) to each of them, q counting on from kSlots.  The caller asserts that the slots fit the workgroup's LDS.
-template <int NT, typename Own>
-__device__ __forceinline__ void hand_over(Grads<NT>& a, float* lds, int wave, int lane, Own&& own) {
+// every lane is handed over, [slot][lane]: the Grads<NT, WA>::kSlots of `a` first (per register acc1, acc2, acc2a with WA, acc3,
+// db1, db2: the order is part of the bits), then the unit's own -- own(f, q) applies x = f(q++, x) to each of them, q counting
+// on from kSlots.  The caller asserts that the slots fit the workgroup's LDS.
+template <int NT, bool WA, typename Own>
+__device__ __forceinline__ void hand_over(Grads<NT, WA>& a, float* lds, int wave, int lane, Own&& own) {
     auto each = [&](auto&& f) {
         int q = 0;
 #pragma unroll
@@ -359,6 +391,7 @@ __device__ __forceinline__ void hand_over(Grads<NT>& a, float* lds, int wave, in
                 for (int nt = 0; nt < NT; ++nt) a.acc1[t][nt][v] = f(q++, a.acc1[t][nt][v]);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) a.acc2[t][u][v] = f(q++, a.acc2[t][u][v]);
+                if constexpr (WA) a.acc2a[t][v] = f(q++, a.acc2a[t][v]);
                 a.acc3[t][v] = f(q++, a.acc3[t][v]);
                 a.db1[t][v] = f(q++, a.db1[t][v]);
                 a.db2[t][v] = f(q++, a.db2[t][v]);
@@ -374,9 +407,10 @@ __device__ __forceinline__ void hand_over(Grads<NT>& a, float* lds, int wave, in
     }
 }
 
-// the network part of the partial up to db2, in the layout of the gradient: plain vector stores.  db3 is the unit's.
-template <int NT>
-__device__ __forceinline__ void store_net(const Grads<NT>& a, float* out, int n_in, int n_out, int n16, int g) {
+// the network part of the partial up to db2, in the layout of the gradient, and with WA dW2a [64][n_act] behind it (at
+// NetOffsets::end): plain vector stores.  db3 is the unit's.
+template <int NT, bool WA>
+__device__ __forceinline__ void store_net(const Grads<NT, WA>& a, float* out, int n_in, int n_out, int n16, int g, int n_act = 0) {
     const NetOffsets o = net_offsets(n_in, n_out);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -389,13 +423,15 @@ __device__ __forceinline__ void store_net(const Grads<NT>& a, float* out, int n_
 #pragma unroll
             for (int u = 0; u < 4; ++u) out[o.W2 + j * H + 16 * u + n16] = a.acc2[t][u][v];
             if (4 * g + v < n_out) out[o.W3 + (4 * g + v) * H + 16 * t + n16] = a.acc3[t][v];
+            if constexpr (WA)
+                if (n16 < n_act) out[o.end + j * n_act + n16] = a.acc2a[t][v];
             if (n16 == 0) { out[o.b1 + j] = a.db1[t][v]; out[o.b2 + j] = a.db2[t][v]; }
         }
 }
 
 // ------------------------------------------------------------------------------------------------------------ float64
 __device__ __forceinline__ double act_prime(double h, int activation) {
-    return activation == 0 ? (h > 0.0 ? 1.0 : 0.0) : 1.0 - h * h;
+    return activation == 0 ? (h > 0.0 ? 1.0 : 0.0) : __builtin_fma(-h, h, 1.0);
 }
 
 // the normalised row into its record
@@ -434,6 +470,16 @@ __device__ __forceinline__ bool net_columns(int e, int n_in, const NetOffsets& o
     else if (e < o.b3) { ca = C::DY + (e - o.W3) / H; cb = C::H2 + (e - o.W3) % H; }
     else if (e < o.end) ca = C::DY + (e - o.b3);
     else return false;
+    return true;
+}
+
+// ... of a gradient that carries dW2a [64][n_act] behind the network's (C: column AS, the row's as)
+template <typename C>
+__device__ __forceinline__ bool net_columns(int e, int n_in, int n_act, const NetOffsets& o, int& ca, int& cb) {
+    if (net_columns<C>(e, n_in, o, ca, cb)) return true;
+    if (e >= o.end + H * n_act) return false;
+    ca = C::D2 + (e - o.end) / n_act;
+    cb = C::AS + (e - o.end) % n_act;
     return true;
 }
 

@@ -4,18 +4,13 @@
 // workgroup; and k_offgrad_reduce<T>, which adds the workgroups' partial sums in a fixed order.
 //
 // Borrowed from ../atacom_policy.h, which this unit includes and does not edit: the LDS layout MlpLdsM, the operand mapping of
-// mlp_forward_mfma, mlp_act16, mlp_act, wave_lds_fence and num<T>.  The backward pass is this unit's own: layer 2 of the critic
-// has two branches, so dW2a = sum delta2 as^T rides on dW2's A operands, TD3's dW1 covers the as columns of [xn | as], and the
-// actor call needs the critic's INPUT gradient, W2a^T delta2 (+ W1[:, D:]^T delta1), which no weight-gradient pass produces.
-//
-// Float32 mappings, one wavefront, one block of 16 rows (lane = (n16, g) = (lane % 16, lane / 16)):
-//   * transposed, H^T = W X^T: lane (n16, g) holds, in register v of tile t, unit 16 t + 4 g + v of row n16 -- for h1, h2 and,
-//     computed the same way from W3^T and W2^T, for delta2 and delta1; the input gradient comes out the same way, element
-//     4 g + v of row n16;
-//   * the weight gradients have the ROW as the K index, so both operands go once through a [16 rows][64 units] buffer of the
-//     wavefront's staging area (put / get, the column rotated by 16 (row % 4) against bank conflicts);
-//   * the accumulators (Grads) stay in registers for the whole walk; at its end the bias sums are added across lanes,
-//     wavefronts 1, 2, 3 hand their registers to wavefront 0 through LDS in that order and wavefront 0 stores the partial.
+// mlp_forward_mfma, mlp_act16, mlp_act, wave_lds_fence and num<T>.  From ../mlp/atacom_mlp_backward.h (namespace
+// atacom_mlp_backward, shared with the fit, trust and soft units), which states the float32 mappings: the row access,
+// the transposition buffers, the backward pass from dy on, the accumulators with their hand-over and store, the float64
+// backward loops, column pairs and accumulation, the slice sum of the reduction and the CH switch.  Layer 2 of the critic has
+// two branches, so its gradient takes the header's WA flag (dW2a = sum delta2 as^T rides on dW2's A operands).  This unit's own:
+// TD3's first-layer input [xn | as], and the critic's INPUT gradient, W2a^T delta2 (+ W1[:, D:]^T delta1), which the actor call
+// needs and no weight-gradient pass produces; it comes out like the deltas, element 4 g + v of row n16 in register v.
 // LDS: one network block MlpLdsM<4 CH, 64, 8>::NET with W2a [64][8] in rows 8 .. 15 of its W3 block (whose outputs are never
 // stored), 8 floats, and 8 KB of staging per wavefront: 63808 bytes.  The kernels are bound to one wavefront per SIMD.
 //
@@ -29,15 +24,7 @@
 
 namespace atacom_offgrad {
 
-typedef atacom::mfma_v4f V4;
 constexpr int kExtra = 8;         // floats after the network block, unused: the block and the staging keep their offsets
-constexpr int kStage = 2048;      // floats of staging per wavefront: two [16][64] transposition buffers
-
-template <typename T>
-struct Rows {
-    const T* p;
-    int64_t so, si;
-};
 
 template <typename T>
 struct Net {
@@ -68,32 +55,6 @@ struct ActorParams {
     int64_t aout_stride, dqout_stride;
     T* workspace;
 };
-
-// the flat number of the call's row r; a row past the end is the last one again
-template <typename P>
-__device__ __forceinline__ int64_t flat_row(const P& p, int64_t r) {
-    const int64_t last = p.n_rows - 1;
-    r = r < last ? r : last;
-    return p.idx ? p.idx[r] : r;
-}
-
-// the host admits at most 2^31 - 1 rows, so the row's (outer, inner) index is a 32-bit division; the offsets are 64-bit
-template <typename T>
-__device__ __forceinline__ const T* row_ptr(const Rows<T>& v, int64_t fr, int64_t n_inner) {
-    const uint32_t o = (uint32_t)fr / (uint32_t)n_inner, i = (uint32_t)fr - o * (uint32_t)n_inner;
-    return v.p + (int64_t)o * v.so + (int64_t)i * v.si;
-}
-
-struct Offsets {
-    int b1, W2, b2, W3, b3, W2a, end;
-};
-
-__host__ __device__ __forceinline__ Offsets offsets(int n_in, int n_out, int n_act) {
-    Offsets o;
-    o.b1 = H * n_in; o.W2 = o.b1 + H; o.b2 = o.W2 + H * H; o.W3 = o.b2 + H; o.b3 = o.W3 + H * n_out; o.W2a = o.b3 + n_out;
-    o.end = o.W2a + H * n_act;
-    return o;
-}
 
 // ------------------------------------------------------------------------------------------------------------ float32
 template <int CH>
@@ -170,6 +131,9 @@ __device__ __forceinline__ void forward_block(const float* __restrict__ net, con
                                               int activation, int n16, int g, V4 (&h1)[4], V4 (&h2)[4], V4& o) {
     using L = LdsM<CH>;
     const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    // layer 1 is the header's layer1 followed by mlp_act16, written out: called as a function it leaves the same instructions
+    // in another schedule, and k_offgrad_actor<float, 6> measured 1.7 % slower (profiles/offpolicy_backward_shared.md); as it
+    // stands the float32 actor kernels are the code they were before the backward pass was shared, byte for byte
     float w1[4][8];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -218,205 +182,6 @@ __device__ __forceinline__ void forward_block(const float* __restrict__ net, con
         }
     }
     o = oa + ob;
-}
-
-// The transposition buffer [16 rows][64 units]: written from the accumulator layout, read as (row, unit) with the lanes of a
-// read on consecutive units.
-__device__ __forceinline__ void put(float* buf, const V4 (&h)[4], int n16, int g) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) *reinterpret_cast<V4*>(buf + n16 * 64 + ((16 * t + 4 * g + 16 * (n16 & 3)) & 63)) = h[t];
-}
-
-__device__ __forceinline__ float get(const float* buf, int row, int unit) {
-    return buf[row * 64 + ((unit + 16 * (row & 3)) & 63)];
-}
-
-// delta <- delta * act'(a), from the activation h = act(a) itself; one wave-uniform branch
-__device__ __forceinline__ void times_act_prime(V4 (&d)[4], const V4 (&h)[4], int activation) {
-    if (activation == 0) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) d[t][v] = h[t][v] > 0.0f ? d[t][v] : 0.0f;
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) d[t][v] *= __builtin_fmaf(-h[t][v], h[t][v], 1.0f);
-    }
-}
-
-__device__ __forceinline__ float sum16(float v) {      // over the 16 lanes that share lane / 16, in every one of them
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-__device__ __forceinline__ float sum64(float v) {      // over the wavefront, in every lane
-    v = sum16(v);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-// a wavefront's accumulators of a network's gradient, for the whole walk; WA: with dW2a (a critic)
-template <int NT, bool WA>
-struct Grads {
-    V4 acc1[4][NT], acc2[4][4], acc2a[4], acc3[4], db1[4], db2[4];
-    static constexpr int kSlots = 16 * (NT + 7 + (WA ? 1 : 0));     // registers of a lane = slots of the hand-over
-
-    __device__ __forceinline__ void zero() {
-        const V4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            acc2a[t] = acc3[t] = db1[t] = db2[t] = z;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc2[t][u] = z;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc1[t][nt] = z;
-        }
-    }
-};
-
-// The backward pass of a block whose dy lies in LDS, [16 rows][8] at t_del + 128 (written by this wavefront, not yet fenced):
-// dW3, delta2, dW2 (and dW2a), delta1, dW1 and the bias gradients into `a`.  xb[s][nt] = element 16 nt + n16 of the first
-// layer's input of row 4 s + g of the block, asb[s] = as[n16] of that row: the B operands whose K index is the row.  t_act and
-// t_del are the wavefront's two transposition buffers, free again when it returns.
-template <int CH, int NT, bool WA>
-__device__ __forceinline__ void backward_block(const float* lds, float* t_act, float* t_del, const V4 (&h1)[4], const V4 (&h2)[4],
-                                               const float (&xb)[4][NT], const float (&asb)[4], int activation, int n16, int g,
-                                               Grads<NT, WA>& a) {
-    using L = LdsM<CH>;
-    const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    put(t_act, h2, n16, g);                                  // dW3's B operand; dy is its A operand
-    atacom::wave_lds_fence();
-    // ---- dW3[k][j] += sum_rows dy[row][k] h2[row][j]: M = k (n16 < 8), N = j, K = the row 4 s + g
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const float ld = t_del[128 + (4 * s + g) * 8 + (n16 & 7)];
-        const float x = n16 < 8 ? ld : 0.0f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            a.acc3[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, get(t_act, 4 * s + g, 16 * u + n16), a.acc3[u], 0, 0, 0);
-    }
-    // ---- delta2 = (W3^T dy) * act'(a2): M = unit, N = row n16, K = the output 4 s + g
-    V4 da[4] = {zero, zero, zero, zero};
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const float b = t_del[128 + n16 * 8 + 4 * s + g];       // dy[4 s + g] of this lane's own row
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            da[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[L::W3 + (4 * s + g) * L::S2 + 16 * u + n16], b, da[u], 0, 0, 0);
-    }
-    times_act_prime(da, h2, activation);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) a.db2[u] += da[u];
-    atacom::wave_lds_fence();                            // dW3 has read both buffers
-    put(t_del, da, n16, g);
-    put(t_act, h1, n16, g);
-    atacom::wave_lds_fence();
-    // ---- dW2[j][i] += sum_rows delta2[row][j] h1[row][i];  dW2a[j][k] += sum_rows delta2[row][j] as[row][k]
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        float x[4], b[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { x[t] = get(t_del, 4 * s + g, 16 * t + n16); b[t] = get(t_act, 4 * s + g, 16 * t + n16); }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a.acc2[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], b[u], a.acc2[t][u], 0, 0, 0);
-            if constexpr (WA) a.acc2a[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], asb[s], a.acc2a[t], 0, 0, 0);
-        }
-    }
-    // ---- delta1 = (W2^T delta2) * act'(a1): K-step (u, v) carries unit j = 16 u + 4 g + v, i.e. register v of da[u]
-    V4 d1[4] = {zero, zero, zero, zero};
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float* wrow = lds + L::W2 + (16 * u + 4 * g + v) * L::S2 + n16;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) d1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[16 * t], da[u][v], d1[t], 0, 0, 0);
-        }
-    times_act_prime(d1, h1, activation);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) a.db1[t] += d1[t];
-    atacom::wave_lds_fence();                            // dW2 has read the deltas
-    put(t_del, d1, n16, g);
-    atacom::wave_lds_fence();
-    // ---- dW1[j][e] += sum_rows delta1[row][j] x1[row][e]
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        float x[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) x[t] = get(t_del, 4 * s + g, 16 * t + n16);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) a.acc1[t][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[t], xb[s][nt], a.acc1[t][nt], 0, 0, 0);
-    }
-    atacom::wave_lds_fence();                            // before the next block writes over the deltas
-}
-
-// the wavefront's sums of the bias gradients over the rows (lane % 16)
-template <int NT, bool WA>
-__device__ __forceinline__ void sum_biases(Grads<NT, WA>& a) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) { a.db1[t][v] = sum16(a.db1[t][v]); a.db2[t][v] = sum16(a.db2[t][v]); }
-}
-
-// The workgroup's sums: wavefronts 1, 2, 3 hand their registers to wavefront 0 through LDS, in that order.  Every register of
-// every lane is handed over, [slot][lane]: the kSlots of `a` first, then the kernel's own -- own(f, q) applies x = f(q++, x) to
-// each of them.  The caller asserts that the slots fit the workgroup's LDS.
-template <int NT, bool WA, typename Own>
-__device__ __forceinline__ void hand_over(Grads<NT, WA>& a, float* lds, int wave, int lane, Own&& own) {
-    auto each = [&](auto&& f) {
-        int q = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) a.acc1[t][nt][v] = f(q++, a.acc1[t][nt][v]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a.acc2[t][u][v] = f(q++, a.acc2[t][u][v]);
-                if constexpr (WA) a.acc2a[t][v] = f(q++, a.acc2a[t][v]);
-                a.acc3[t][v] = f(q++, a.acc3[t][v]);
-                a.db1[t][v] = f(q++, a.db1[t][v]);
-                a.db2[t][v] = f(q++, a.db2[t][v]);
-            }
-        own(f, q);
-    };
-    __syncthreads();
-    for (int w = 1; w < kWaves; ++w) {
-        if (wave == w) each([&](int q, float v) { lds[q * 64 + lane] = v; return v; });
-        __syncthreads();
-        if (wave == 0) each([&](int q, float v) { return v + lds[q * 64 + lane]; });
-        __syncthreads();
-    }
-}
-
-// the partial up to db2 and dW2a, in the layout of the gradient: plain vector stores.  db3 and the statistics are the kernel's.
-template <int NT, bool WA>
-__device__ __forceinline__ void store_net(const Grads<NT, WA>& a, float* out, int n_in, int n_out, int n_act, int n16, int g) {
-    const Offsets o = offsets(n_in, n_out, n_act);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int j = 16 * t + 4 * g + v;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                if (16 * nt + n16 < n_in) out[j * n_in + 16 * nt + n16] = a.acc1[t][nt][v];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) out[o.W2 + j * H + 16 * u + n16] = a.acc2[t][u][v];
-            if (4 * g + v < n_out) out[o.W3 + (4 * g + v) * H + 16 * t + n16] = a.acc3[t][v];
-            if constexpr (WA)
-                if (n16 < n_act) out[o.W2a + j * n_act + n16] = a.acc2a[t][v];
-            if (n16 == 0) { out[o.b1 + j] = a.db1[t][v]; out[o.b2 + j] = a.db2[t][v]; }
-        }
 }
 
 template <int CH>
@@ -480,7 +245,7 @@ __device__ __forceinline__ void critic_f32(const CriticParams<float>& p) {
             st += live ? d * d : 0.0f;
             *reinterpret_cast<V4*>(t_del + 128 + n16 * 8) = V4{dy, 0.0f, 0.0f, 0.0f};
             *reinterpret_cast<V4*>(t_del + 128 + n16 * 8 + 4) = V4{0.0f, 0.0f, 0.0f, 0.0f};
-            backward_block<CH, NT, true>(lds, t_act, t_del, h1, h2, xb, asb, net.activation, n16, g, acc);
+            backward<CH, NT, true>(lds, t_act, t_del, h1, h2, xb, asb, net.activation, n16, g, acc);
         }
     }
     sum_biases(acc);
@@ -494,12 +259,12 @@ __device__ __forceinline__ void critic_f32(const CriticParams<float>& p) {
     if (wave != 0) return;
     const int64_t Q = partial_size(net.n1, 1, p.n_act);
     float* out = p.workspace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Q;
-    store_net(acc, out, net.n1, 1, p.n_act, n16, g);
+    store_net(acc, out, net.n1, 1, n16, g, p.n_act);
     if (lane == 0) {
-        const Offsets o = offsets(net.n1, 1, p.n_act);
-        out[o.b3] = db3;
-        out[o.end] = st;
-        out[o.end + 1] = out[o.end + 2] = out[o.end + 3] = 0.0f;
+        out[net_offsets(net.n1, 1).b3] = db3;
+        float* stats = out + (Q - kStats);
+        stats[0] = st;
+        stats[1] = stats[2] = stats[3] = 0.0f;
     }
 }
 
@@ -517,12 +282,12 @@ __device__ __forceinline__ void actor_f32(const ActorParams<float>& p) {
     const int ka = (p.n_act + 3) / 4;
     const V4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
 
-    Grads<NT, false> acc;
+    Grads<NT> acc;
     acc.zero();
     float db3[NK], st = 0.0f;
 #pragma unroll
     for (int k = 0; k < NK; ++k) db3[k] = 0.0f;
-    const float noa[2] = {0.0f, 0.0f}, nob[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const float noa[2] = {0.0f, 0.0f};
 
     const int64_t n_tiles = (p.n_rows + kRowsF32 - 1) / kRowsF32, step = (int64_t)gridDim.x * kWaves, last = p.n_rows - 1;
     const int64_t rounds = (n_tiles + step - 1) / step;         // uniform per workgroup: every wavefront reaches every barrier
@@ -676,14 +441,14 @@ __device__ __forceinline__ void actor_f32(const ActorParams<float>& p) {
             }
             V4 h1[4], h2[4], o;
             forward_block<CH>(lds, xin, noa, 0, p.actor.activation, n16, g, h1, h2, o);
-            backward_block<CH, NT, false>(lds, t_act, t_del, h1, h2, xb, nob, p.actor.activation, n16, g, acc);
+            backward<CH, NT>(lds, t_act, t_del, h1, h2, xb, p.actor.activation, n16, g, acc);
         }
     }
     sum_biases(acc);
 #pragma unroll
     for (int k = 0; k < NK; ++k) db3[k] = sum64(db3[k]);
     st = sum16(st);
-    static_assert((Grads<NT, false>::kSlots + NK + 1) * 64 <= kLds, "the hand-over fits the workgroup's LDS");
+    static_assert((Grads<NT>::kSlots + NK + 1) * 64 <= kLds, "the hand-over fits the workgroup's LDS");
     hand_over(acc, lds, wave, lane, [&](auto&& f, int q) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) db3[k] = f(q++, db3[k]);
@@ -692,9 +457,9 @@ __device__ __forceinline__ void actor_f32(const ActorParams<float>& p) {
     if (wave != 0) return;
     const int64_t Q = partial_size(p.n_obs, p.n_act, 0);
     float* out = p.workspace + (int64_t)blockIdx.x * Q;
-    store_net(acc, out, p.n_obs, p.n_act, 0, n16, g);
+    store_net(acc, out, p.n_obs, p.n_act, n16, g);
     if (lane == 0) {
-        const Offsets o = offsets(p.n_obs, p.n_act, 0);
+        const NetOffsets o = net_offsets(p.n_obs, p.n_act);
 #pragma unroll
         for (int k = 0; k < NK; ++k)
             if (k < p.n_act) out[o.b3 + k] = db3[k];
@@ -706,11 +471,7 @@ __device__ __forceinline__ void actor_f32(const ActorParams<float>& p) {
 // ------------------------------------------------------------------------------------------------------------ float64
 // A workgroup takes 16 rows at a time, sixteen threads a row; the weights are read from memory, the rows' activations and
 // deltas lie in LDS as one record per row, and every thread owns the entries tid, tid + 256, ... of the partial, each the sum
-// over rows of the product of two columns of the records.
-__device__ __forceinline__ double act_prime(double h, int activation) {
-    return activation == 0 ? (h > 0.0 ? 1.0 : 0.0) : __builtin_fma(-h, h, 1.0);
-}
-
+// over rows of the product of two columns of the records (the header's backward_f64, net_columns and accumulate_f64).
 // columns of a record: the network whose gradient is taken (h1 | h2 | delta1 | delta2 | its first-layer input | as | dy), the
 // statistic, 1 and 0; the actor kernel appends its critic's columns
 struct Rec {
@@ -722,18 +483,12 @@ struct RecActor : Rec {
     static constexpr int CH1 = Rec::SIZE, CH2 = CH1 + H, CX = CH2 + H, GM = CX + 32, SIZE = GM + NK;
 };
 
-// the two columns whose product, summed over the rows, is entry e of the partial; past its end: 0 * 1
-__device__ __forceinline__ void entry_columns(int e, int n_in, int n_out, int n_act, const Offsets& o, int& ca, int& cb) {
+// the two columns whose product, summed over the rows, is entry e of the partial: the gradient's, then the statistic; past its
+// end: 0 * 1
+__device__ __forceinline__ void entry_columns(int e, int n_in, int n_act, const NetOffsets& o, int& ca, int& cb) {
     ca = Rec::ZERO;
     cb = Rec::ONE;
-    if (e < o.b1) { ca = Rec::D1 + e / n_in; cb = Rec::X + e % n_in; }
-    else if (e < o.W2) ca = Rec::D1 + (e - o.b1);
-    else if (e < o.b2) { ca = Rec::D2 + (e - o.W2) / H; cb = Rec::H1 + (e - o.W2) % H; }
-    else if (e < o.W3) ca = Rec::D2 + (e - o.b2);
-    else if (e < o.b3) { ca = Rec::DY + (e - o.W3) / H; cb = Rec::H2 + (e - o.W3) % H; }
-    else if (e < o.W2a) ca = Rec::DY + (e - o.b3);
-    else if (e < o.end) { ca = Rec::D2 + (e - o.W2a) / n_act; cb = Rec::AS + (e - o.W2a) % n_act; }
-    else if (e == o.end) ca = Rec::ST;
+    if (!net_columns<Rec>(e, n_in, n_act, o, ca, cb) && e == o.end + H * n_act) ca = Rec::ST;
 }
 
 constexpr int kMaxQ = H * 32 + H + H * H + H + H * NK + NK + H * NK + kStats, kNQ = (kMaxQ + kBlock - 1) / kBlock;
@@ -758,32 +513,6 @@ __device__ __forceinline__ void hidden_f64(const Net<double>& n, double* me, int
     __syncthreads();
 }
 
-// delta2 and delta1 of the thread's row from its dy, h2 and h1
-__device__ __forceinline__ void backward_f64(const Net<double>& n, double* me, bool live, int c) {
-    if (live)
-        for (int j = c; j < H; j += 16) {
-            double a = 0.0;
-            for (int k = 0; k < n.n_out; ++k) a = __builtin_fma(n.W3[k * H + j], me[Rec::DY + k], a);
-            me[Rec::D2 + j] = a * act_prime(me[Rec::H2 + j], n.activation);
-        }
-    __syncthreads();
-    if (live)
-        for (int i = c; i < H; i += 16) {
-            double a = 0.0;
-            for (int j = 0; j < H; ++j) a = __builtin_fma(n.W2[j * H + i], me[Rec::D2 + j], a);
-            me[Rec::D1 + i] = a * act_prime(me[Rec::H1 + i], n.activation);
-        }
-    __syncthreads();
-}
-
-template <int SIZE>
-__device__ __forceinline__ void accumulate_f64(const double* rec, int rows, const int (&ca)[kNQ], const int (&cb)[kNQ], double (&acc)[kNQ]) {
-#pragma unroll
-    for (int q = 0; q < kNQ; ++q)
-        for (int rr = 0; rr < rows; ++rr) acc[q] = __builtin_fma(rec[rr * SIZE + ca[q]], rec[rr * SIZE + cb[q]], acc[q]);
-    __syncthreads();
-}
-
 __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
     constexpr int R = kRowsF64;
     using C = Rec;
@@ -798,13 +527,13 @@ __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
 #undef OFFGRAD_PICK
     const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
     const int Q = (int)partial_size(net.n1, 1, p.n_act);
-    const Offsets o = offsets(net.n1, 1, p.n_act);
+    const NetOffsets o = net_offsets(net.n1, 1);
     int ca[kNQ], cb[kNQ];
     double acc[kNQ];
 #pragma unroll
     for (int q = 0; q < kNQ; ++q) {
         acc[q] = 0.0;
-        entry_columns(tid + kBlock * q, net.n1, 1, p.n_act, o, ca[q], cb[q]);
+        entry_columns(tid + kBlock * q, net.n1, p.n_act, o, ca[q], cb[q]);
     }
     const int64_t n_tiles = (p.n_rows + R - 1) / R;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -836,13 +565,10 @@ __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
             me[C::ST] = d * d;
         }
         __syncthreads();
-        backward_f64(net, me, live, c);
-        accumulate_f64<C::SIZE>(rec, rows, ca, cb, acc);
+        backward_f64<C>(net, me, live, c);
+        accumulate_f64<C>(rec, rows, ca, cb, acc);
     }
-    double* out = p.workspace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Q;
-#pragma unroll
-    for (int q = 0; q < kNQ; ++q)
-        if (tid + kBlock * q < Q) out[tid + kBlock * q] = acc[q];
+    store_f64(p.workspace + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Q, Q, tid, acc);
 }
 
 __device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
@@ -855,13 +581,13 @@ __device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
     const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
     const int k = p.n_act, D = p.n_obs;
     const int Q = (int)partial_size(D, k, 0);
-    const Offsets o = offsets(D, k, 0);
+    const NetOffsets o = net_offsets(D, k);
     int ca[kNQ], cb[kNQ];
     double acc[kNQ];
 #pragma unroll
     for (int q = 0; q < kNQ; ++q) {
         acc[q] = 0.0;
-        entry_columns(tid + kBlock * q, D, k, 0, o, ca[q], cb[q]);
+        entry_columns(tid + kBlock * q, D, 0, o, ca[q], cb[q]);
     }
     const int64_t n_tiles = (p.n_rows + R - 1) / R;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -933,13 +659,10 @@ __device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
             me[C::DY + c] = dm;
         }
         __syncthreads();
-        backward_f64(A, me, live, c);
-        accumulate_f64<C::SIZE>(rec, rows, ca, cb, acc);
+        backward_f64<C>(A, me, live, c);
+        accumulate_f64<C>(rec, rows, ca, cb, acc);
     }
-    double* out = p.workspace + (int64_t)blockIdx.x * Q;
-#pragma unroll
-    for (int q = 0; q < kNQ; ++q)
-        if (tid + kBlock * q < Q) out[tid + kBlock * q] = acc[q];
+    store_f64(p.workspace + (int64_t)blockIdx.x * Q, Q, tid, acc);
 }
 
 // one wavefront per SIMD: the float32 kernels keep up to 160 accumulator registers next to their operands
@@ -955,9 +678,8 @@ __global__ __launch_bounds__(kBlock, 1) void k_offgrad_actor(const ActorParams<T
     else actor_f64(p);
 }
 
-// grad and stats of network blockIdx.y from its partials: a workgroup takes kReduceValues consecutive values; slice s of its
-// threads adds the partials s, s + kReduceSlices, ... in that order, the slices' sums are added in the order of s, and the sum
-// is divided by the number of rows
+// grad and stats of network blockIdx.y from its partials: a workgroup takes kReduceValues consecutive values, each summed in the
+// fixed order of sum_partials and divided by the number of rows
 template <typename T>
 struct ReduceParams {
     const T* ws;
@@ -969,18 +691,9 @@ struct ReduceParams {
 
 template <typename T>
 __global__ __launch_bounds__(kReduceBlock) void k_offgrad_reduce(const ReduceParams<T> p) {
-    __shared__ T part[kReduceSlices][kReduceValues];
-    const int v = threadIdx.x % kReduceValues, slice = threadIdx.x / kReduceValues;
-    const int i = blockIdx.x * kReduceValues + v;
-    const T* ws = p.ws + (int64_t)blockIdx.y * p.blocks * p.q_size;
-    T s = T(0);
-    if (i < p.q_size)
-        for (int b = slice; b < p.blocks; b += kReduceSlices) s += ws[(int64_t)b * p.q_size + i];
-    part[slice][v] = s;
-    __syncthreads();
-    if (slice != 0 || i >= p.q_size) return;
-#pragma unroll
-    for (int k = 1; k < kReduceSlices; ++k) s += part[k][v];
+    const int i = blockIdx.x * kReduceValues + threadIdx.x % kReduceValues;
+    T s;
+    if (!sum_partials(p.ws + (int64_t)blockIdx.y * p.blocks * p.q_size, p.blocks, p.q_size, p.q_size, i, s)) return;
     s = s / p.m;
     T* grad = blockIdx.y ? p.grad[1] : p.grad[0];
     T* stats = blockIdx.y ? p.stats[1] : p.stats[0];
@@ -1008,15 +721,6 @@ void reduce(const void* ws, void* const (&grad)[2], void* const (&stats)[2], int
     hipLaunchKernelGGL((k_offgrad_reduce<T>), dim3((q + kReduceValues - 1) / kReduceValues, n_nets), dim3(kReduceBlock), 0, s, r);
 }
 
-#define OFFGRAD_GO(KERNEL, GRID, CH) \
-    case CH: hipLaunchKernelGGL((KERNEL<T, CH>), GRID, dim3(kBlock), 0, s, p); break
-#define OFFGRAD_SWITCH(KERNEL, GRID, n1)                                                                                  \
-    switch (((n1) + 3) / 4) {                                                                                             \
-        OFFGRAD_GO(KERNEL, GRID, 1); OFFGRAD_GO(KERNEL, GRID, 2); OFFGRAD_GO(KERNEL, GRID, 3); OFFGRAD_GO(KERNEL, GRID, 4); \
-        OFFGRAD_GO(KERNEL, GRID, 5); OFFGRAD_GO(KERNEL, GRID, 6); OFFGRAD_GO(KERNEL, GRID, 7); OFFGRAD_GO(KERNEL, GRID, 8); \
-        default: return ATACOM_OFFGRAD_E_UNSUPPORTED;                                                                     \
-    }
-
 template <typename T>
 int launch_critic(const CriticCall& c, int blocks, hipStream_t s) {
     CriticParams<T> p{};
@@ -1026,7 +730,10 @@ int launch_critic(const CriticCall& c, int blocks, hipStream_t s) {
     p.obs = rows_of<T>(c.obs); p.action = rows_of<T>(c.action);
     p.target = (const T*)c.target; p.target_stride = c.target_stride; p.workspace = (T*)c.workspace;
     const int n1 = c.net[0].n1;
-    OFFGRAD_SWITCH(k_offgrad_critic, dim3(blocks, c.n_nets), n1)
+    if (!with_ch(n1, [&](auto ch) {
+            hipLaunchKernelGGL((k_offgrad_critic<T, decltype(ch)::value>), dim3(blocks, c.n_nets), dim3(kBlock), 0, s, p);
+        }))
+        return ATACOM_OFFGRAD_E_UNSUPPORTED;
     reduce<T>(c.workspace, c.grad, c.stats, c.n_nets, blocks, (int)partial_size(n1, 1, c.n_act), c.n_rows, s);
     return ATACOM_OFFGRAD_OK;
 }
@@ -1039,15 +746,15 @@ int launch_actor(const ActorCall& c, int blocks, hipStream_t s) {
     p.obs = rows_of<T>(c.obs);
     p.aout = (T*)c.action_out; p.aout_stride = c.action_out_stride; p.dqout = (T*)c.dqda_out; p.dqout_stride = c.dqda_out_stride;
     p.workspace = (T*)c.workspace;
-    OFFGRAD_SWITCH(k_offgrad_actor, dim3(blocks), c.critic.n1)   // the critic's first layer: the widest of the call
+    if (!with_ch(c.critic.n1, [&](auto ch) {   // the critic's first layer: the widest of the call
+            hipLaunchKernelGGL((k_offgrad_actor<T, decltype(ch)::value>), dim3(blocks), dim3(kBlock), 0, s, p);
+        }))
+        return ATACOM_OFFGRAD_E_UNSUPPORTED;
     void* const grad[2] = {c.grad, c.grad};
     void* const stats[2] = {c.stats, c.stats};
     reduce<T>(c.workspace, grad, stats, 1, blocks, (int)partial_size(c.n_obs, c.n_act, 0), c.n_rows, s);
     return ATACOM_OFFGRAD_OK;
 }
-
-#undef OFFGRAD_SWITCH
-#undef OFFGRAD_GO
 
 }  // namespace
 

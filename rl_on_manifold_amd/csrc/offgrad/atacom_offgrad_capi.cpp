@@ -10,83 +10,14 @@
 #define ATACOM_CAPI_E_HIP ATACOM_OFFGRAD_E_HIP
 #include "../atacom_capi_common.h"        // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 #include "../atacom_mlp_host.h"           // mlp_abi_copy
+#define ATACOM_CAPI_E_INVALID ATACOM_OFFGRAD_E_INVALID
+#define ATACOM_CAPI_LIB(X) ATACOM_OFFGRAD_##X
+#include "../mlp/atacom_view_checks.h"   // dec, Extent, Named, extent, strided, flat, overlap, check_strides, check_row_stride, check_aligned,
+                                          // check_overlaps, check_workspace, check_head
 
 namespace {
 
 constexpr int INVALID = ATACOM_OFFGRAD_E_INVALID, UNSUPPORTED = ATACOM_OFFGRAD_E_UNSUPPORTED;
-
-std::string dec(long long v) { return std::to_string(v); }
-
-// [lo, hi) in bytes
-struct Extent {
-    intptr_t lo, hi;
-    std::string name;
-};
-
-Extent extent(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, int esize, const char* name) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t so = n_outer > 1 ? v.stride_outer * (n_outer - 1) : 0, si = n_inner > 1 ? v.stride_inner * (n_inner - 1) : 0;
-    (so < 0 ? lo : hi) += so;
-    (si < 0 ? lo : hi) += si;
-    const intptr_t base = (intptr_t)v.ptr;
-    return {base + (intptr_t)(lo * esize), base + (intptr_t)((hi + 1) * esize), name};
-}
-
-// M rows of `width` at ptr[r * stride]
-Extent strided(const void* p, int64_t rows, int64_t stride, int width, int esize, const char* name) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t s = rows > 1 ? stride * (rows - 1) : 0;
-    (s < 0 ? lo : hi) += s;
-    return {(intptr_t)p + (intptr_t)(lo * esize), (intptr_t)p + (intptr_t)((hi + 1) * esize), name};
-}
-
-Extent flat(const void* p, int64_t bytes, const std::string& name) { return {(intptr_t)p, (intptr_t)p + (intptr_t)bytes, name}; }
-
-bool overlap(const Extent& a, const Extent& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// rows must not run into each other; a view is an input and may repeat a row (stride 0)
-int check_strides(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, const char* name, const std::string& w) {
-    const struct { int64_t n, st; const char* dim; } dims[2] = {{n_outer, v.stride_outer, "stride_outer"}, {n_inner, v.stride_inner, "stride_inner"}};
-    for (const auto& d : dims) {
-        if (d.n <= 1) continue;
-        const int64_t mag = d.st < 0 ? -d.st : d.st;
-        if (mag >= width || d.st == 0) continue;
-        return fail(INVALID, w + ": " + name + "." + d.dim + " = " + dec(d.st) + " is below the row width " + dec(width));
-    }
-    return 0;
-}
-
-int check_row_stride(int64_t rows, int64_t stride, int width, bool output, const char* name, const std::string& w) {
-    if (rows <= 1) return 0;
-    const int64_t mag = stride < 0 ? -stride : stride;
-    if (mag >= width || (!output && stride == 0)) return 0;
-    return fail(INVALID, w + ": " + name + "_stride = " + dec(stride) + " is below the row width " + dec(width));
-}
-
-int check_aligned(const void* p, int esize, const char* name, const std::string& w) {
-    if ((intptr_t)p % esize == 0) return 0;
-    return fail(INVALID, w + ": " + name + " must be aligned to the dtype");
-}
-
-// what every call shares: sizes, idx.  *rows = M.
-int check_head(int32_t device, int32_t dtype, int32_t n_blocks, int64_t n_outer, int64_t n_inner, const int64_t* idx, int64_t n_idx,
-               const std::string& w, int64_t* rows) {
-    if (device < 0) return fail(INVALID, w + ": device = " + dec(device));
-    if (dtype != ATACOM_OFFGRAD_F32 && dtype != ATACOM_OFFGRAD_F64) return fail(UNSUPPORTED, w + ": no kernel for dtype " + dec(dtype));
-    if (n_outer < 1) return fail(INVALID, w + ": n_outer must be >= 1, got " + dec(n_outer));
-    if (n_inner < 1) return fail(INVALID, w + ": n_inner must be >= 1, got " + dec(n_inner));
-    if (n_outer > ATACOM_OFFGRAD_MAX_ROWS / n_inner)
-        return fail(UNSUPPORTED, w + ": n_outer * n_inner = " + dec(n_outer) + " * " + dec(n_inner) + " rows is too many (at most " +
-                                     dec(ATACOM_OFFGRAD_MAX_ROWS) + " a call)");
-    if (n_blocks < 0) return fail(INVALID, w + ": n_blocks must be >= 1, or 0 for the library's choice, got " + dec(n_blocks));
-    if (n_blocks > ATACOM_OFFGRAD_MAX_BLOCKS)
-        return fail(UNSUPPORTED, w + ": n_blocks = " + dec(n_blocks) + " exceeds the launch grid (" + dec(ATACOM_OFFGRAD_MAX_BLOCKS) + ")");
-    if (idx && n_idx < 1) return fail(INVALID, w + ": n_idx must be >= 1 with idx, got " + dec(n_idx));
-    if (idx && n_idx > ATACOM_OFFGRAD_MAX_ROWS)
-        return fail(UNSUPPORTED, w + ": n_idx = " + dec(n_idx) + " rows is too many (at most " + dec(ATACOM_OFFGRAD_MAX_ROWS) + " a call)");
-    *rows = idx ? n_idx : n_outer * n_inner;
-    return 0;
-}
 
 int check_critic(const atacom_offgrad_critic& c, int esize, const std::string& w, atacom_offgrad::NetDesc* d) {
     if (c.kind != ATACOM_OFFGRAD_DDPG && c.kind != ATACOM_OFFGRAD_TD3)
@@ -110,29 +41,9 @@ int check_critic(const atacom_offgrad_critic& c, int esize, const std::string& w
     return 0;
 }
 
-// an output against every input and the outputs before it
-int check_overlaps(const std::vector<Extent>& outs, const std::vector<Extent>& ins, const std::string& w) {
-    for (size_t o = 0; o < outs.size(); ++o) {
-        for (const auto& in : ins)
-            if (overlap(outs[o], in)) return fail(INVALID, w + ": " + outs[o].name + " overlaps " + in.name);
-        for (size_t p = 0; p < o; ++p)
-            if (overlap(outs[o], outs[p])) return fail(INVALID, w + ": " + outs[p].name + " overlaps " + outs[o].name);
-    }
-    return 0;
-}
-
 size_t workspace_bytes(int esize, int n_nets, int64_t partial, int64_t blocks) {
     const size_t raw = (size_t)n_nets * (size_t)blocks * (size_t)partial * (size_t)esize;
     return (raw + 255) / 256 * 256;
-}
-
-int check_workspace(const void* ws, size_t have, size_t need, const std::string& w) {
-    if (!ws) return fail(INVALID, w + ": null argument (workspace)");
-    if ((intptr_t)ws % 16) return fail(INVALID, w + ": workspace must be aligned to 16 bytes");
-    if (have < need)
-        return fail(INVALID, w + ": workspace_bytes = " + dec((long long)have) + " is below the " + dec((long long)need) +
-                                 " that atacom_offgrad_workspace_size gives");
-    return 0;
 }
 
 }  // namespace
@@ -199,11 +110,11 @@ int atacom_offgrad_critic_gradient(const atacom_offgrad_critic_args* a) {
     const int64_t blocks = atacom_offgrad::effective_blocks(a->n_blocks, rows, f64);
     const int64_t n_grad = atacom_offgrad::grad_size(n1, 1, k);
     const size_t need = workspace_bytes(esize, a->n_critics, n_grad + ATACOM_OFFGRAD_STATS, blocks);
-    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, w)) return rc;
-    std::vector<Extent> ins = {extent(a->obs, no, ni, D, esize, "obs"), extent(a->action, no, ni, k, esize, "action"),
+    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, "atacom_offgrad_workspace_size", w)) return rc;
+    std::vector<Named> ins = {extent(a->obs, no, ni, D, esize, "obs"), extent(a->action, no, ni, k, esize, "action"),
                                strided(a->target, rows, a->target_stride, 1, esize, "target")};
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
-    std::vector<Extent> outs;
+    std::vector<Named> outs;
     for (int j = 0; j < a->n_critics; ++j) {
         outs.push_back(flat(a->grad[j], n_grad * esize, "grad[" + dec(j) + "]"));
         outs.push_back(flat(a->stats[j], ATACOM_OFFGRAD_STATS * esize, "stats[" + dec(j) + "]"));
@@ -276,10 +187,10 @@ int atacom_offgrad_actor_gradient(const atacom_offgrad_actor_args* a) {
     const int64_t blocks = atacom_offgrad::effective_blocks(a->n_blocks, rows, f64);
     const int64_t n_grad = atacom_offgrad::grad_size(D, k, 0);
     const size_t need = workspace_bytes(esize, 1, n_grad + ATACOM_OFFGRAD_STATS, blocks);
-    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, w)) return rc;
-    std::vector<Extent> ins = {extent(a->obs, no, ni, D, esize, "obs")};
+    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, "atacom_offgrad_workspace_size", w)) return rc;
+    std::vector<Named> ins = {extent(a->obs, no, ni, D, esize, "obs")};
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
-    std::vector<Extent> outs = {flat(a->grad, n_grad * esize, "grad"), flat(a->stats, ATACOM_OFFGRAD_STATS * esize, "stats")};
+    std::vector<Named> outs = {flat(a->grad, n_grad * esize, "grad"), flat(a->stats, ATACOM_OFFGRAD_STATS * esize, "stats")};
     if (a->action_out) outs.push_back(strided(a->action_out, rows, a->action_out_stride, k, esize, "action_out"));
     if (a->dqda_out) outs.push_back(strided(a->dqda_out, rows, a->dqda_out_stride, k, esize, "dqda_out"));
     outs.push_back(flat(a->workspace, (int64_t)need, "workspace"));

@@ -12,78 +12,14 @@
 #define ATACOM_CAPI_E_HIP ATACOM_OFFPOLICY_E_HIP
 #include "../atacom_capi_common.h"        // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 #include "../atacom_mlp_host.h"           // mlp_abi_copy
+#define ATACOM_CAPI_E_INVALID ATACOM_OFFPOLICY_E_INVALID
+#define ATACOM_CAPI_LIB(X) ATACOM_OFFPOLICY_##X
+#include "../mlp/atacom_view_checks.h"   // dec, Extent, Named, extent, strided, flat, overlap, check_strides, check_row_stride, check_aligned,
+                                          // check_overlaps, check_workspace, check_head
 
 namespace {
 
 constexpr int INVALID = ATACOM_OFFPOLICY_E_INVALID, UNSUPPORTED = ATACOM_OFFPOLICY_E_UNSUPPORTED;
-
-std::string dec(long long v) { return std::to_string(v); }
-
-// [lo, hi) in bytes
-struct Extent {
-    intptr_t lo, hi;
-    std::string name;
-};
-
-Extent extent(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, int esize, const char* name) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t so = n_outer > 1 ? v.stride_outer * (n_outer - 1) : 0, si = n_inner > 1 ? v.stride_inner * (n_inner - 1) : 0;
-    (so < 0 ? lo : hi) += so;
-    (si < 0 ? lo : hi) += si;
-    const intptr_t base = (intptr_t)v.ptr;
-    return {base + (intptr_t)(lo * esize), base + (intptr_t)((hi + 1) * esize), name};
-}
-
-// M rows of `width` at ptr[r * stride]
-Extent strided(const void* p, int64_t rows, int64_t stride, int width, int esize, const char* name) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t s = rows > 1 ? stride * (rows - 1) : 0;
-    (s < 0 ? lo : hi) += s;
-    return {(intptr_t)p + (intptr_t)(lo * esize), (intptr_t)p + (intptr_t)((hi + 1) * esize), name};
-}
-
-Extent flat(const void* p, int64_t bytes, const std::string& name) { return {(intptr_t)p, (intptr_t)p + (intptr_t)bytes, name}; }
-
-bool overlap(const Extent& a, const Extent& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// rows must not run into each other; a view is an input and may repeat a row (stride 0)
-int check_strides(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, const char* name, const std::string& w) {
-    const struct { int64_t n, st; const char* dim; } dims[2] = {{n_outer, v.stride_outer, "stride_outer"}, {n_inner, v.stride_inner, "stride_inner"}};
-    for (const auto& d : dims) {
-        if (d.n <= 1) continue;
-        const int64_t mag = d.st < 0 ? -d.st : d.st;
-        if (mag >= width || d.st == 0) continue;
-        return fail(INVALID, w + ": " + name + "." + d.dim + " = " + dec(d.st) + " is below the row width " + dec(width));
-    }
-    return 0;
-}
-
-int check_row_stride(int64_t rows, int64_t stride, int width, bool output, const char* name, const std::string& w) {
-    if (rows <= 1) return 0;
-    const int64_t mag = stride < 0 ? -stride : stride;
-    if (mag >= width || (!output && stride == 0)) return 0;
-    return fail(INVALID, w + ": " + name + "_stride = " + dec(stride) + " is below the row width " + dec(width));
-}
-
-// what both network calls share: struct head, sizes, idx.  *rows = M.
-int check_head(int32_t device, int32_t dtype, int32_t n_blocks, int64_t n_outer, int64_t n_inner, const int64_t* idx, int64_t n_idx,
-               const std::string& w, int64_t* rows) {
-    if (device < 0) return fail(INVALID, w + ": device = " + dec(device));
-    if (dtype != ATACOM_OFFPOLICY_F32 && dtype != ATACOM_OFFPOLICY_F64) return fail(UNSUPPORTED, w + ": no kernel for dtype " + dec(dtype));
-    if (n_outer < 1) return fail(INVALID, w + ": n_outer must be >= 1, got " + dec(n_outer));
-    if (n_inner < 1) return fail(INVALID, w + ": n_inner must be >= 1, got " + dec(n_inner));
-    if (n_outer > ATACOM_OFFPOLICY_MAX_ROWS / n_inner)
-        return fail(UNSUPPORTED, w + ": n_outer * n_inner = " + dec(n_outer) + " * " + dec(n_inner) + " rows is too many (at most " +
-                                     dec(ATACOM_OFFPOLICY_MAX_ROWS) + " a call)");
-    if (n_blocks < 0) return fail(INVALID, w + ": n_blocks must be >= 1, or 0 for the library's choice, got " + dec(n_blocks));
-    if (n_blocks > ATACOM_OFFPOLICY_MAX_BLOCKS)
-        return fail(UNSUPPORTED, w + ": n_blocks = " + dec(n_blocks) + " exceeds the launch grid (" + dec(ATACOM_OFFPOLICY_MAX_BLOCKS) + ")");
-    if (idx && n_idx < 1) return fail(INVALID, w + ": n_idx must be >= 1 with idx, got " + dec(n_idx));
-    if (idx && n_idx > ATACOM_OFFPOLICY_MAX_ROWS)
-        return fail(UNSUPPORTED, w + ": n_idx = " + dec(n_idx) + " rows is too many (at most " + dec(ATACOM_OFFPOLICY_MAX_ROWS) + " a call)");
-    *rows = idx ? n_idx : n_outer * n_inner;
-    return 0;
-}
 
 int check_critic(const atacom_offpolicy_critic& c, const std::string& w, atacom_offpolicy::NetDesc* d) {
     if (c.kind != ATACOM_OFFPOLICY_DDPG && c.kind != ATACOM_OFFPOLICY_TD3)
@@ -99,17 +35,6 @@ int check_critic(const atacom_offpolicy_critic& c, const std::string& w, atacom_
     if (!c.W1 || !c.b1 || !c.W2 || !c.b2 || !c.W2a || !c.W3 || !c.b3)
         return fail(INVALID, w + ": null argument (a weight or bias of the critic)");
     *d = atacom_offpolicy::NetDesc{c.W1, c.b1, c.W2, c.b2, c.W2a, c.W3, c.b3, c.obs_shift, c.obs_scale, c.act_scale, n1, 1, c.activation, 0};
-    return 0;
-}
-
-// an output against every input and the outputs before it
-int check_overlaps(const std::vector<Extent>& outs, const std::vector<Extent>& ins, const std::string& w) {
-    for (size_t o = 0; o < outs.size(); ++o) {
-        for (const auto& in : ins)
-            if (overlap(outs[o], in)) return fail(INVALID, w + ": " + outs[o].name + " overlaps " + in.name);
-        for (size_t p = 0; p < o; ++p)
-            if (overlap(outs[o], outs[p])) return fail(INVALID, w + ": " + outs[p].name + " overlaps " + outs[o].name);
-    }
     return 0;
 }
 
@@ -159,7 +84,7 @@ int atacom_offpolicy_q(const atacom_offpolicy_q_args* a) {
     if (int rc = check_strides(a->obs, no, ni, D, "obs", w)) return rc;
     if (int rc = check_strides(a->action, no, ni, k, "action", w)) return rc;
     if (int rc = check_row_stride(rows, a->q_stride, 1, true, "q", w)) return rc;
-    std::vector<Extent> ins = {extent(a->obs, no, ni, D, esize, "obs"), extent(a->action, no, ni, k, esize, "action")};
+    std::vector<Named> ins = {extent(a->obs, no, ni, D, esize, "obs"), extent(a->action, no, ni, k, esize, "action")};
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
     if (int rc = check_overlaps({strided(a->q, rows, a->q_stride, 1, esize, "q")}, ins, w)) return rc;
 
@@ -224,11 +149,11 @@ int atacom_offpolicy_target(const atacom_offpolicy_target_args* a) {
     if (int rc = check_row_stride(rows, a->y_stride, 1, true, "y", w)) return rc;
     if (a->action_out)
         if (int rc = check_row_stride(rows, a->action_out_stride, k, true, "action_out", w)) return rc;
-    std::vector<Extent> ins = {extent(a->next_obs, no, ni, D, esize, "next_obs"), extent(a->reward, no, ni, 1, esize, "reward"),
+    std::vector<Named> ins = {extent(a->next_obs, no, ni, D, esize, "next_obs"), extent(a->reward, no, ni, 1, esize, "reward"),
                                extent(a->absorbing, no, ni, 1, esize, "absorbing")};
     if (a->eps) ins.push_back(strided(a->eps, rows, a->eps_stride, k, esize, "eps"));
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
-    std::vector<Extent> outs = {strided(a->y, rows, a->y_stride, 1, esize, "y")};
+    std::vector<Named> outs = {strided(a->y, rows, a->y_stride, 1, esize, "y")};
     if (a->action_out) outs.push_back(strided(a->action_out, rows, a->action_out_stride, k, esize, "action_out"));
     if (int rc = check_overlaps(outs, ins, w)) return rc;
 
@@ -256,7 +181,7 @@ int atacom_offpolicy_soft_update(const atacom_offpolicy_soft_update_args* a) {
         return fail(INVALID, w + ": n_pairs = " + dec(a->n_pairs) + " is outside 1 .. " + dec(ATACOM_OFFPOLICY_MAX_PAIRS));
     if (!(a->tau >= 0.0 && a->tau <= 1.0)) return fail(INVALID, w + ": tau must be in [0, 1], got " + std::to_string(a->tau));
     const int esize = a->dtype == ATACOM_OFFPOLICY_F64 ? 8 : 4;
-    std::vector<Extent> targets, onlines;
+    std::vector<Named> targets, onlines;
     for (int k = 0; k < a->n_pairs; ++k) {
         const atacom_offpolicy_pair& p = a->pairs[k];
         const std::string pw = "pairs[" + dec(k) + "]";

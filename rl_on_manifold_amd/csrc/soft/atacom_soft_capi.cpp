@@ -11,82 +11,20 @@
 #define ATACOM_CAPI_E_HIP ATACOM_SOFT_E_HIP
 #include "../atacom_capi_common.h"        // g_err, fail, HIP_TRY, DeviceGuard, ON_DEVICE
 #include "../atacom_mlp_host.h"           // mlp_abi_copy
+#define ATACOM_CAPI_E_INVALID ATACOM_SOFT_E_INVALID
+#define ATACOM_CAPI_LIB(X) ATACOM_SOFT_##X
+#include "../mlp/atacom_view_checks.h"   // dec, Extent, Named, extent, strided, flat, overlap, check_strides, check_row_stride, check_aligned,
+                                          // check_overlaps, check_workspace, check_head
 
 namespace {
 
 constexpr int INVALID = ATACOM_SOFT_E_INVALID, UNSUPPORTED = ATACOM_SOFT_E_UNSUPPORTED;
 
-std::string dec(long long v) { return std::to_string(v); }
-
-// [lo, hi) in bytes
-struct Extent {
-    intptr_t lo, hi;
-    std::string name;
-};
-
-Extent extent(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, int esize, const char* name) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t so = n_outer > 1 ? v.stride_outer * (n_outer - 1) : 0, si = n_inner > 1 ? v.stride_inner * (n_inner - 1) : 0;
-    (so < 0 ? lo : hi) += so;
-    (si < 0 ? lo : hi) += si;
-    const intptr_t base = (intptr_t)v.ptr;
-    return {base + (intptr_t)(lo * esize), base + (intptr_t)((hi + 1) * esize), name};
-}
-
-// M rows of `width` at ptr[r * stride]
-Extent strided(const void* p, int64_t rows, int64_t stride, int width, int esize, const char* name) {
-    int64_t lo = 0, hi = width - 1;
-    const int64_t s = rows > 1 ? stride * (rows - 1) : 0;
-    (s < 0 ? lo : hi) += s;
-    return {(intptr_t)p + (intptr_t)(lo * esize), (intptr_t)p + (intptr_t)((hi + 1) * esize), name};
-}
-
-Extent flat(const void* p, int64_t bytes, const std::string& name) { return {(intptr_t)p, (intptr_t)p + (intptr_t)bytes, name}; }
-
-bool overlap(const Extent& a, const Extent& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-// rows must not run into each other; a view is an input and may repeat a row (stride 0)
-int check_strides(const atacom_evaluate_view& v, int64_t n_outer, int64_t n_inner, int width, const char* name, const std::string& w) {
-    const struct { int64_t n, st; const char* dim; } dims[2] = {{n_outer, v.stride_outer, "stride_outer"}, {n_inner, v.stride_inner, "stride_inner"}};
-    for (const auto& d : dims) {
-        if (d.n <= 1) continue;
-        const int64_t mag = d.st < 0 ? -d.st : d.st;
-        if (mag >= width || d.st == 0) continue;
-        return fail(INVALID, w + ": " + name + "." + d.dim + " = " + dec(d.st) + " is below the row width " + dec(width));
-    }
-    return 0;
-}
-
-int check_row_stride(int64_t rows, int64_t stride, int width, bool output, const char* name, const std::string& w) {
-    if (rows <= 1) return 0;
-    const int64_t mag = stride < 0 ? -stride : stride;
-    if (mag >= width || (!output && stride == 0)) return 0;
-    return fail(INVALID, w + ": " + name + "_stride = " + dec(stride) + " is below the row width " + dec(width));
-}
-
-int check_aligned(const void* p, int esize, const std::string& name, const std::string& w) {
-    if ((intptr_t)p % esize == 0) return 0;
-    return fail(INVALID, w + ": " + name + " must be aligned to the dtype");
-}
-
-// what every row call shares: sizes, idx.  *rows = M.
-int check_head(int32_t device, int32_t dtype, int32_t n_blocks, int64_t n_outer, int64_t n_inner, const int64_t* idx, int64_t n_idx,
-               const std::string& w, int64_t* rows) {
-    if (device < 0) return fail(INVALID, w + ": device = " + dec(device));
-    if (dtype != ATACOM_SOFT_F32 && dtype != ATACOM_SOFT_F64) return fail(UNSUPPORTED, w + ": no kernel for dtype " + dec(dtype));
-    if (n_outer < 1) return fail(INVALID, w + ": n_outer must be >= 1, got " + dec(n_outer));
-    if (n_inner < 1) return fail(INVALID, w + ": n_inner must be >= 1, got " + dec(n_inner));
-    if (n_outer > ATACOM_SOFT_MAX_ROWS / n_inner)
-        return fail(UNSUPPORTED, w + ": n_outer * n_inner = " + dec(n_outer) + " * " + dec(n_inner) + " rows is too many (at most " +
-                                     dec(ATACOM_SOFT_MAX_ROWS) + " a call)");
-    if (n_blocks < 0) return fail(INVALID, w + ": n_blocks must be >= 1, or 0 for the library's choice, got " + dec(n_blocks));
-    if (n_blocks > ATACOM_SOFT_MAX_BLOCKS)
-        return fail(UNSUPPORTED, w + ": n_blocks = " + dec(n_blocks) + " exceeds the launch grid (" + dec(ATACOM_SOFT_MAX_BLOCKS) + ")");
-    if (idx && n_idx < 1) return fail(INVALID, w + ": n_idx must be >= 1 with idx, got " + dec(n_idx));
-    if (idx && n_idx > ATACOM_SOFT_MAX_ROWS)
-        return fail(UNSUPPORTED, w + ": n_idx = " + dec(n_idx) + " rows is too many (at most " + dec(ATACOM_SOFT_MAX_ROWS) + " a call)");
+// what every row call shares, and the alignment of idx.  *rows = M.
+int check_row_head(int32_t device, int32_t dtype, int32_t n_blocks, int64_t n_outer, int64_t n_inner, const int64_t* idx, int64_t n_idx,
+                   const std::string& w, int64_t* rows) {
+    if (int rc = check_head(device, dtype, n_blocks, n_outer, n_inner, idx, n_idx, w, rows)) return rc;
     if ((intptr_t)idx % 8) return fail(INVALID, w + ": idx must be aligned to the dtype");
-    *rows = idx ? n_idx : n_outer * n_inner;
     return 0;
 }
 
@@ -144,33 +82,13 @@ int check_policy(const atacom_mlp& in, int D, int k, int esize, const std::strin
     return 0;
 }
 
-// an output against every input and the outputs before it
-int check_overlaps(const std::vector<Extent>& outs, const std::vector<Extent>& ins, const std::string& w) {
-    for (size_t o = 0; o < outs.size(); ++o) {
-        for (const auto& in : ins)
-            if (overlap(outs[o], in)) return fail(INVALID, w + ": " + outs[o].name + " overlaps " + in.name);
-        for (size_t p = 0; p < o; ++p)
-            if (overlap(outs[o], outs[p])) return fail(INVALID, w + ": " + outs[p].name + " overlaps " + outs[o].name);
-    }
-    return 0;
-}
-
 size_t workspace_bytes(int esize, int n_nets, int64_t partial, int64_t blocks) {
     const size_t raw = (size_t)n_nets * (size_t)blocks * (size_t)partial * (size_t)esize;
     return (raw + 255) / 256 * 256;
 }
 
-int check_workspace(const void* ws, size_t have, size_t need, const std::string& w) {
-    if (!ws) return fail(INVALID, w + ": null argument (workspace)");
-    if ((intptr_t)ws % 16) return fail(INVALID, w + ": workspace must be aligned to 16 bytes");
-    if (have < need)
-        return fail(INVALID, w + ": workspace_bytes = " + dec((long long)have) + " is below the " + dec((long long)need) +
-                                 " that atacom_soft_workspace_size gives");
-    return 0;
-}
-
 // an optional per-row output: alignment, stride, extent
-int add_out(const void* p, int64_t rows, int64_t stride, int width, int esize, const char* name, const std::string& w, std::vector<Extent>* outs) {
+int add_out(const void* p, int64_t rows, int64_t stride, int width, int esize, const char* name, const std::string& w, std::vector<Named>* outs) {
     if (!p) return 0;
     if (int rc = check_aligned(p, esize, name, w)) return rc;
     if (int rc = check_row_stride(rows, stride, width, true, name, w)) return rc;
@@ -180,7 +98,7 @@ int add_out(const void* p, int64_t rows, int64_t stride, int width, int esize, c
 
 // eps, act_scale, act_shift, log_alpha of a call: presence, alignment and their extents as inputs
 int check_squash(const void* eps, int64_t eps_stride, const void* act_scale, const void* act_shift, const void* log_alpha, int64_t rows, int k,
-                 int esize, const std::string& w, std::vector<Extent>* ins) {
+                 int esize, const std::string& w, std::vector<Named>* ins) {
     if (!eps) return fail(INVALID, w + ": null argument (eps)");
     if (!log_alpha) return fail(INVALID, w + ": null argument (log_alpha)");
     if (int rc = check_aligned(eps, esize, "eps", w)) return rc;
@@ -224,7 +142,7 @@ int atacom_soft_target(const atacom_soft_target_args* a) {
     if (a->struct_size != sizeof(atacom_soft_target_args))
         return fail(INVALID, w + ": struct_size = " + dec(a->struct_size) + ", this library expects " + dec(sizeof(atacom_soft_target_args)));
     int64_t rows = 0;
-    if (int rc = check_head(a->device, a->dtype, a->n_blocks, a->n_outer, a->n_inner, a->idx, a->n_idx, w, &rows)) return rc;
+    if (int rc = check_row_head(a->device, a->dtype, a->n_blocks, a->n_outer, a->n_inner, a->idx, a->n_idx, w, &rows)) return rc;
     if (a->n_critics != 2) return fail(UNSUPPORTED, w + ": n_critics = " + dec(a->n_critics) + " (SAC has two critics)");
     const bool f64 = a->dtype == ATACOM_SOFT_F64;
     const int esize = f64 ? 8 : 4;
@@ -240,11 +158,11 @@ int atacom_soft_target(const atacom_soft_target_args* a) {
     if (int rc = check_aligned(a->reward.ptr, esize, "reward", w)) return rc;
     if (int rc = check_aligned(a->absorbing.ptr, esize, "absorbing", w)) return rc;
     if (int rc = check_strides(a->next_obs, no, ni, D, "next_obs", w)) return rc;
-    std::vector<Extent> ins = {extent(a->next_obs, no, ni, D, esize, "next_obs"), extent(a->reward, no, ni, 1, esize, "reward"),
+    std::vector<Named> ins = {extent(a->next_obs, no, ni, D, esize, "next_obs"), extent(a->reward, no, ni, 1, esize, "reward"),
                                extent(a->absorbing, no, ni, 1, esize, "absorbing")};
     if (int rc = check_squash(a->eps, a->eps_stride, a->act_scale, a->act_shift, a->log_alpha, rows, k, esize, w, &ins)) return rc;
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
-    std::vector<Extent> outs;
+    std::vector<Named> outs;
     if (int rc = add_out(a->y, rows, a->y_stride, 1, esize, "y", w, &outs)) return rc;
     if (int rc = add_out(a->action_out, rows, a->action_out_stride, k, esize, "action_out", w, &outs)) return rc;
     if (int rc = add_out(a->logp_out, rows, a->logp_out_stride, 1, esize, "logp_out", w, &outs)) return rc;
@@ -269,7 +187,7 @@ int atacom_soft_critic_gradient(const atacom_soft_critic_args* a) {
     if (a->struct_size != sizeof(atacom_soft_critic_args))
         return fail(INVALID, w + ": struct_size = " + dec(a->struct_size) + ", this library expects " + dec(sizeof(atacom_soft_critic_args)));
     int64_t rows = 0;
-    if (int rc = check_head(a->device, a->dtype, a->n_blocks, a->n_outer, a->n_inner, a->idx, a->n_idx, w, &rows)) return rc;
+    if (int rc = check_row_head(a->device, a->dtype, a->n_blocks, a->n_outer, a->n_inner, a->idx, a->n_idx, w, &rows)) return rc;
     if (a->n_critics != 1 && a->n_critics != 2) return fail(INVALID, w + ": n_critics = " + dec(a->n_critics) + " (1 or 2)");
     const bool f64 = a->dtype == ATACOM_SOFT_F64;
     const int esize = f64 ? 8 : 4;
@@ -295,11 +213,11 @@ int atacom_soft_critic_gradient(const atacom_soft_critic_args* a) {
     const int64_t blocks = atacom_soft::effective_blocks(a->n_blocks, rows, f64);
     const int64_t n_grad = atacom_soft::grad_size(n1, 1);
     const size_t need = workspace_bytes(esize, a->n_critics, n_grad + ATACOM_SOFT_STATS, blocks);
-    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, w)) return rc;
-    std::vector<Extent> ins = {extent(a->obs, no, ni, D, esize, "obs"), extent(a->action, no, ni, k, esize, "action"),
+    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, "atacom_soft_workspace_size", w)) return rc;
+    std::vector<Named> ins = {extent(a->obs, no, ni, D, esize, "obs"), extent(a->action, no, ni, k, esize, "action"),
                                strided(a->target, rows, a->target_stride, 1, esize, "target")};
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
-    std::vector<Extent> outs;
+    std::vector<Named> outs;
     for (int j = 0; j < a->n_critics; ++j) {
         outs.push_back(flat(a->grad[j], n_grad * esize, "grad[" + dec(j) + "]"));
         outs.push_back(flat(a->stats[j], ATACOM_SOFT_STATS * esize, "stats[" + dec(j) + "]"));
@@ -323,7 +241,7 @@ int atacom_soft_actor_gradient(const atacom_soft_actor_args* a) {
     if (a->struct_size != sizeof(atacom_soft_actor_args))
         return fail(INVALID, w + ": struct_size = " + dec(a->struct_size) + ", this library expects " + dec(sizeof(atacom_soft_actor_args)));
     int64_t rows = 0;
-    if (int rc = check_head(a->device, a->dtype, a->n_blocks, a->n_outer, a->n_inner, a->idx, a->n_idx, w, &rows)) return rc;
+    if (int rc = check_row_head(a->device, a->dtype, a->n_blocks, a->n_outer, a->n_inner, a->idx, a->n_idx, w, &rows)) return rc;
     const bool f64 = a->dtype == ATACOM_SOFT_F64;
     const int esize = f64 ? 8 : 4;
     atacom_soft::ActorCall c = {};
@@ -339,14 +257,14 @@ int atacom_soft_actor_gradient(const atacom_soft_actor_args* a) {
     if (int rc = check_aligned(a->grad_sigma, esize, "grad_sigma", w)) return rc;
     if (int rc = check_aligned(a->stats, esize, "stats", w)) return rc;
     if (int rc = check_strides(a->obs, no, ni, D, "obs", w)) return rc;
-    std::vector<Extent> ins = {extent(a->obs, no, ni, D, esize, "obs")};
+    std::vector<Named> ins = {extent(a->obs, no, ni, D, esize, "obs")};
     if (int rc = check_squash(a->eps, a->eps_stride, a->act_scale, a->act_shift, a->log_alpha, rows, k, esize, w, &ins)) return rc;
     if (a->idx) ins.push_back(flat(a->idx, a->n_idx * 8, "idx"));
     const int64_t blocks = atacom_soft::effective_blocks(a->n_blocks, rows, f64);
     const int64_t n_grad = atacom_soft::grad_size(D, k);
     const size_t need = workspace_bytes(esize, 2, n_grad + ATACOM_SOFT_STATS, blocks);
-    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, w)) return rc;
-    std::vector<Extent> outs = {flat(a->grad_mu, n_grad * esize, "grad_mu"), flat(a->grad_sigma, n_grad * esize, "grad_sigma"),
+    if (int rc = check_workspace(a->workspace, a->workspace_bytes, need, "atacom_soft_workspace_size", w)) return rc;
+    std::vector<Named> outs = {flat(a->grad_mu, n_grad * esize, "grad_mu"), flat(a->grad_sigma, n_grad * esize, "grad_sigma"),
                                 flat(a->stats, ATACOM_SOFT_STATS * esize, "stats")};
     if (int rc = add_out(a->action_out, rows, a->action_out_stride, k, esize, "action_out", w, &outs)) return rc;
     if (int rc = add_out(a->logp_out, rows, a->logp_out_stride, 1, esize, "logp_out", w, &outs)) return rc;
@@ -383,8 +301,8 @@ int atacom_soft_alpha_step(const atacom_soft_alpha_args* a) {
     if (!(a->lr >= 0.0) || !std::isfinite(a->lr)) return fail(INVALID, w + ": lr must be >= 0 and finite");
     if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0)) return fail(INVALID, w + ": beta1 and beta2 must be in [0, 1)");
     if (!(a->eps > 0.0) || !std::isfinite(a->eps)) return fail(INVALID, w + ": eps must be > 0 and finite");
-    const std::vector<Extent> ins = {flat(a->grad, esize, "grad")};
-    const std::vector<Extent> outs = {flat(a->log_alpha, esize, "log_alpha"), flat(a->state, ATACOM_SOFT_ALPHA_STATE, "state")};
+    const std::vector<Named> ins = {flat(a->grad, esize, "grad")};
+    const std::vector<Named> outs = {flat(a->log_alpha, esize, "log_alpha"), flat(a->state, ATACOM_SOFT_ALPHA_STATE, "state")};
     if (int rc = check_overlaps(outs, ins, w)) return rc;
     atacom_soft::AlphaCall c = {a->dtype, a->log_alpha, a->grad, a->state, a->lr, a->beta1, a->beta2, a->eps};
     ON_DEVICE(a);

@@ -7,7 +7,9 @@ import os
 import abi_tools as abi
 
 OWN = {'atacom_fit.h', 'atacom_fit.hip', 'atacom_fit_capi.cpp', 'atacom_fit_hip.h'}
-SHARED = {'atacom_mlp_backward.h', 'atacom_view_checks.h'}          # csrc/mlp/: headers it shares with libatacom_trust.so
+# csrc/mlp/: headers it shares with libatacom_trust.so, libatacom_offgrad.so and libatacom_soft.so -- the view checks with
+# libatacom_offpolicy.so too
+SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
 
 
 def test_extensions_is_the_one_row():
@@ -33,7 +35,7 @@ def test_the_include_closure_follows_the_borrowed_headers_into_csrc():
     assert all(os.path.isabs(p) and os.path.isfile(p) for p in src)
     names = {os.path.basename(p) for p in src}
     assert OWN | {'atacom_policy.h', 'atacom_mlp_host.h', 'atacom_capi_common.h'} <= names
-    assert names == OWN | SHARED | {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h',
+    assert names == OWN | set(SHARED) | {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h',
                                     'atacom_hip.h', 'atacom_evaluate_hip.h'}
     # the borrowed files are the ones directly inside csrc/ and include/, not copies
     where = {os.path.basename(p): os.path.dirname(p) for p in src}
@@ -63,11 +65,11 @@ def test_a_touched_file_makes_fit_stale_and_its_own_files_only_fit(monkeypatch):
     assert [n for n in every if build.stale(n)] == ['evaluate', 'fit']
     touched[:] = ['atacom_returns.hip']
     assert not build.stale('fit')
-    # the shared headers of csrc/mlp/: exactly fit and trust, none of the seven and not optim
+    # the shared headers of csrc/mlp/: exactly the libraries named above, none of the seven and not optim
     libs += [t.lib for t in build.ADDITIONS.values()]
-    for name in sorted(SHARED):
+    for name, users in sorted(SHARED.items()):
         touched[:] = [name]
-        assert [n for n in every + list(build.ADDITIONS) if build.stale(n)] == ['fit', 'trust'], name
+        assert [n for n in every + list(build.ADDITIONS) if build.stale(n)] == users, name
 
 
 def test_the_seven_are_still_the_seven_and_build_extensions_builds_the_rest():

@@ -1,8 +1,9 @@
 """CPU-only checks of the 'soft' row of build.ADDITIONS, the open table of rl_on_manifold_amd/build.py: the row is there with its
-own properties, build(), stale() and sources() take its key, its include closure is its own files and the borrowed headers (the
-network's LDS layout, the host description, the scaffolding, the view type) with nothing of csrc/mlp/, fit, trust, optim,
-offpolicy or offgrad, a touched file of its own makes no other library stale, its unit is compiled without contraction, and the
-two pinned tables are as they were.  Nothing here counts the rows of ADDITIONS.  No source is edited."""
+own properties, build(), stale() and sources() take its key, its include closure is exactly its own files, the borrowed headers
+(the network's LDS layout, the host description, the scaffolding, the view type) and the two headers of csrc/mlp/ (the backward
+pass and the view checks), with nothing of fit, trust, optim, offpolicy or offgrad, a touched file of its own makes no other
+library stale, a touched header of csrc/mlp/ exactly the libraries that share it, its unit is compiled without contraction, and
+the two pinned tables are as they were.  Nothing here counts the rows of ADDITIONS.  No source is edited."""
 import importlib
 import os
 
@@ -11,6 +12,8 @@ import abi_tools as abi
 OWN = {'atacom_soft.h', 'atacom_soft.hip', 'atacom_soft_capi.cpp', 'atacom_soft_hip.h'}
 BORROWED = {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h', 'atacom_hip.h',
             'atacom_evaluate_hip.h'}
+# csrc/mlp/: the backward pass it shares with fit, trust and offgrad; the view checks, which offpolicy includes too
+SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
 
 
 def test_the_soft_row_and_what_follows_from_its_key():
@@ -40,14 +43,16 @@ def test_the_include_closure_is_its_own_files_and_the_borrowed_headers():
     src = build.sources('soft')
     assert src == build.sources(build.ADDITIONS['soft'])
     assert all(os.path.isabs(p) and os.path.isfile(p) for p in src)
-    assert {os.path.basename(p) for p in src} == OWN | BORROWED
+    assert {os.path.basename(p) for p in src} == OWN | BORROWED | set(SHARED)
     where = {os.path.basename(p): os.path.dirname(p) for p in src}
     for name in ('atacom_policy.h', 'atacom_capi_common.h', 'atacom_mlp_host.h'):
         assert where[name] == build.CSRC, name
     assert where['atacom_soft_hip.h'] == abi.INCLUDE and where['atacom_evaluate_hip.h'] == abi.INCLUDE
-    # nothing of csrc/mlp/ or of the gradient, trust-region, optimiser and off-policy libraries, and it lends nothing
-    assert not any(os.path.basename(d) in ('mlp', 'fit', 'trust', 'optim', 'offpolicy', 'offgrad') for d in where.values())
-    assert not any(w in name for name in where for w in ('fit', 'trust', 'optim', 'offpolicy', 'offgrad', 'backward', 'view_checks'))
+    for name in SHARED:
+        assert where[name] == os.path.join(build.CSRC, 'mlp'), name
+    # nothing of the gradient, trust-region, optimiser and off-policy libraries, and it lends nothing
+    assert not any(os.path.basename(d) in ('fit', 'trust', 'optim', 'offpolicy', 'offgrad') for d in where.values())
+    assert not any(w in name for name in where for w in ('fit', 'trust', 'optim', 'offpolicy', 'offgrad'))
     for table in (build.TARGETS, build.EXTENSIONS, build.ADDITIONS):
         for name, t in table.items():
             if name != 'soft':
@@ -72,10 +77,14 @@ def test_a_touched_file_of_its_own_makes_only_soft_stale(monkeypatch):
     touched[:] = ['atacom_evaluate_hip.h']
     assert build.stale('soft')
     for other in ('atacom_fit.hip', 'atacom_fit_hip.h', 'atacom_trust.hip', 'atacom_optim.hip', 'atacom_optim_hip.h', 'atacom_returns.hip',
-                  'atacom_evaluate.hip', 'atacom_mlp_backward.h', 'atacom_view_checks.h', 'atacom_offpolicy.hip', 'atacom_offpolicy.h',
-                  'atacom_offpolicy_hip.h', 'atacom_offgrad.hip', 'atacom_offgrad.h', 'atacom_offgrad_hip.h'):
+                  'atacom_evaluate.hip', 'atacom_offpolicy.hip', 'atacom_offpolicy.h', 'atacom_offpolicy_hip.h', 'atacom_offgrad.hip',
+                  'atacom_offgrad.h', 'atacom_offgrad_hip.h'):
         touched[:] = [other]
         assert not build.stale('soft'), other
+    # the shared headers of csrc/mlp/: exactly the libraries named above and nothing else
+    for name, users in sorted(SHARED.items()):
+        touched[:] = [name]
+        assert [n for n in every if build.stale(n)] == users, name
 
 
 def test_the_pinned_tables_are_unchanged_and_build_additions_builds_the_row():

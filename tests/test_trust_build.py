@@ -10,7 +10,9 @@ import abi_tools as abi
 OWN = {'atacom_trust.h', 'atacom_trust.hip', 'atacom_trust_capi.cpp', 'atacom_trust_hip.h'}
 BORROWED = {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h', 'atacom_hip.h',
             'atacom_evaluate_hip.h'}
-SHARED = {'atacom_mlp_backward.h', 'atacom_view_checks.h'}          # csrc/mlp/: headers it shares with libatacom_fit.so
+# csrc/mlp/: headers it shares with libatacom_fit.so, libatacom_offgrad.so and libatacom_soft.so -- the view checks with
+# libatacom_offpolicy.so too
+SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
 
 
 def test_the_trust_row_and_what_follows_from_its_key():
@@ -35,7 +37,7 @@ def test_the_include_closure_is_its_own_files_and_the_borrowed_headers():
     src = build.sources('trust')
     assert src == build.sources(build.ADDITIONS['trust'])
     assert all(os.path.isabs(p) and os.path.isfile(p) for p in src)
-    assert {os.path.basename(p) for p in src} == OWN | BORROWED | SHARED
+    assert {os.path.basename(p) for p in src} == OWN | BORROWED | set(SHARED)
     where = {os.path.basename(p): os.path.dirname(p) for p in src}
     assert where['atacom_policy.h'] == build.CSRC and where['atacom_capi_common.h'] == build.CSRC
     for name in SHARED:
@@ -69,10 +71,10 @@ def test_a_touched_file_of_its_own_makes_only_trust_stale(monkeypatch):
     for other in ('atacom_fit.hip', 'atacom_fit_hip.h', 'atacom_fit.h', 'atacom_optim.hip', 'atacom_returns.hip'):
         touched[:] = [other]
         assert not build.stale('trust'), other
-    # the shared headers of csrc/mlp/: exactly fit and trust, none of the seven and not optim
-    for name in sorted(SHARED):
+    # the shared headers of csrc/mlp/: exactly the libraries named above, none of the seven and not optim
+    for name, users in sorted(SHARED.items()):
         touched[:] = [name]
-        assert [n for n in every if build.stale(n)] == ['fit', 'trust'], name
+        assert [n for n in every if build.stale(n)] == users, name
 
 
 def test_the_pinned_tables_are_unchanged_and_build_additions_builds_the_row():
