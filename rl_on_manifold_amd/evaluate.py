@@ -13,46 +13,7 @@ here is differentiable.  No numerics here, and no fall-back: a missing library i
 import torch
 
 from . import _lib_evaluate as _le
-from .returns import _overlap, _stream
-
-_DTYPES = {torch.float32: _le.F32, torch.float64: _le.F64}
-
-
-def _check_rows(t, name, lead, width, ref):
-    """`t` is [*lead, width] with contiguous rows, of the dtype and on the device of `ref`."""
-    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(lead) + (width,):
-        raise ValueError("%s must be a tensor of shape %s, got %s" % (name, tuple(lead) + (width,),
-                                                                      tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
-    if t.dtype != ref.dtype or t.device != ref.device:
-        raise ValueError("%s must be a %s tensor on %s, got %s on %s" % (name, ref.dtype, ref.device, t.dtype, t.device))
-    if width > 1 and t.stride(-1) != 1:
-        raise ValueError("the %d elements of a row of %s must be contiguous (stride %d)" % (width, name, t.stride(-1)))
-    return t
-
-
-def _launches(lead, strides):
-    """The leading dimensions `lead` shared by several tensors with per-tensor `strides` -> [(offsets, n_outer, n_inner,
-    [(stride_outer, stride_inner)])]: dimensions of size 1 dropped, neighbours that merge in every tensor merged, and what is
-    still beyond two dimensions walked here, one launch per index."""
-    dims = [(n, [s[j] for s in strides]) for j, n in enumerate(lead) if n != 1]
-    merged = []
-    for n, st in dims:
-        if merged and all(a == n * b for a, b in zip(merged[-1][1], st)):
-            merged[-1] = (merged[-1][0] * n, st)
-        else:
-            merged.append((n, st))
-    out = []
-
-    def walk(ds, offs):
-        if len(ds) <= 2:
-            ds = [(1, [0] * len(strides))] * (2 - len(ds)) + ds
-            out.append((offs, ds[0][0], ds[1][0], list(zip(ds[0][1], ds[1][1]))))
-            return
-        for i in range(ds[0][0]):
-            walk(ds[1:], [o + i * s for o, s in zip(offs, ds[0][1])])
-
-    walk(merged, [0] * len(strides))
-    return out
+from ._rows import check_rows, checked_blocks, column, columns, fill, launches, needs_gpu, no_overlap, records_of, rows_of, run
 
 
 def evaluate_rows(net, x, action=None, *, y=None, logp=None, n_blocks=0):
@@ -61,12 +22,7 @@ def evaluate_rows(net, x, action=None, *, y=None, logp=None, n_blocks=0):
     leading dimensions and may be strided views (the columns of packed records) whose rows are contiguous; outputs overlap
     neither an input nor each other.  n_blocks workgroups walk the row tiles (0: the library chooses).  The general entry:
     evaluate_mlp, gaussian_log_prob and the *_from_records functions are written with it."""
-    if not isinstance(x, torch.Tensor) or x.dim() < 1:
-        raise ValueError("x must be a tensor [..., n_in]")
-    if x.device.type != 'cuda':
-        raise ValueError("the kernels of libatacom_evaluate.so run on a GPU; got tensors on %s" % x.device)
-    if x.dtype not in _DTYPES:
-        raise ValueError("x must be float32 or float64, got %s" % x.dtype)
+    lead = rows_of(x, 'x')
     if y is None and logp is None:
         raise ValueError("neither y nor logp is given: nothing to compute")
     if logp is not None and (action is None or net.tensors.get('std') is None):
@@ -74,34 +30,23 @@ def evaluate_rows(net, x, action=None, *, y=None, logp=None, n_blocks=0):
     m = net.as_struct_on(x.device, x.dtype)
     if x.shape[-1] != m.n_in:
         raise ValueError("x has rows of %d where the network takes %d" % (x.shape[-1], m.n_in))
-    lead = tuple(x.shape[:-1])
-    if any(n == 0 for n in lead):
-        raise ValueError("x holds no rows: %s" % (tuple(x.shape),))
-    ts = [_check_rows(x, 'x', lead, m.n_in, x)]
-    slots = ['x']
+    ins, outs = [(check_rows(x, 'x', lead, m.n_in, x), 'x')], []
     if logp is not None:
-        ts.append(_check_rows(action, 'action', lead, m.n_out, x))
-        slots.append('action')
+        ins.append((check_rows(action, 'action', lead, m.n_out, x), 'action'))
     if y is not None:
-        ts.append(_check_rows(y, 'y', lead, m.n_out, x))
-        slots.append('y')
+        outs.append((check_rows(y, 'y', lead, m.n_out, x), 'y'))
     if logp is not None:
-        ts.append(_check_rows(logp.unsqueeze(-1) if isinstance(logp, torch.Tensor) else logp, 'logp', lead, 1, x))
-        slots.append('logp')
-    outs = [t for t, s in zip(ts, slots) if s in ('y', 'logp')]
-    for o in outs:
-        for t, s in zip(ts, slots):
-            if t is not o and _overlap(o, t):
-                raise ValueError("an output overlaps %s: the call does not work in place" % s)
+        outs.append((check_rows(column(logp), 'logp', lead, 1, x), 'logp'))
+    no_overlap(outs, ins)
+    n_blocks = checked_blocks(n_blocks, _le.MAX_BLOCKS)
+    needs_gpu(x, 'evaluate')
+    ts, slots = zip(*ins + outs)
     a = _le.new_args()
-    a.device, a.dtype, a.n_blocks, a.net = x.device.index, _DTYPES[x.dtype], int(n_blocks), m
-    a.stream = _stream(x.device.index)
-    lib, size = _le.load(), x.element_size()
-    for offs, n_outer, n_inner, strides in _launches(lead, [t.stride()[:-1] for t in ts]):
-        a.n_outer, a.n_inner = n_outer, n_inner
-        for t, s, off, (so, si) in zip(ts, slots, offs, strides):
-            setattr(a, s, _le.View(t.data_ptr() + off * size, so, si))
-        _le.check(lib.atacom_evaluate_mlp(a))
+    a.net = m
+    lib = _le.load()
+    for launch in launches(lead, [t.stride()[:-1] for t in ts]):
+        fill(a, x, n_blocks, launch, slots, ts)
+        run(a, lib.atacom_evaluate_mlp, _le.check, x)
 
 
 def _out(t, name, lead, width, x):
@@ -131,12 +76,6 @@ def gaussian_log_prob(policy, obs, action, *, out=None, mean_out=None):
     return lp
 
 
-def _records(layout, g, F, what):
-    if not isinstance(g, torch.Tensor) or g.dim() not in (3, 4) or g.shape[-1] != F:
-        raise ValueError("%s must be [W, T, Bm, %d] or [T, Bm, %d], got %s" % (what, F, F, tuple(getattr(g, 'shape', ()))))
-    return g
-
-
 def _critic(layout, critic):
     if int(torch.as_tensor(critic.tensors['W3']).shape[0]) != 1 or int(torch.as_tensor(critic.tensors['W1']).shape[1]) != layout.D:
         raise ValueError("the critic must map the %d observation elements to one value" % layout.D)
@@ -145,7 +84,7 @@ def _critic(layout, critic):
 def values_from_records(layout, g, critic):
     """(v, v_next) = the critic on the obs and next_obs columns of full packed records g [W, T, Bm, F] (or [T, Bm, F]) of
     `layout` (a RecordLayout), read in place -> two tensors [W, T, Bm] (or [T, Bm]): the arguments of gae_from_records."""
-    g = _records(layout, g, layout.F, 'full records')
+    g = records_of(g, layout.F, 'full records')
     _critic(layout, critic)
     v, vn = torch.empty(g.shape[:-1], dtype=g.dtype, device=g.device), torch.empty(g.shape[:-1], dtype=g.dtype, device=g.device)
     evaluate_rows(critic, g[..., layout.fields['obs']], y=v.unsqueeze(-1))
@@ -159,7 +98,7 @@ def values_from_compact(layout, records, ends, n_ends, critic):
     (or [M, D + 2]; None or M = 0: v_ends is None) -> [W, T + 1, Bm] and [W, M]: the two arguments of gae_from_compact.  The
     critic sees (T + 1) Bm + M rows per rank and next_obs is never built.  Every one of the M rows is evaluated; n_ends, which
     says how many of them are valid, is for gae_from_compact to apply."""
-    records = _records(layout, records, layout.Fc, 'compact records')
+    records = records_of(records, layout.Fc, 'compact records')
     if records.shape[-3] != layout.T + 1:
         raise ValueError("compact records must hold %d rows of time (the tail included), got %d" % (layout.T + 1, records.shape[-3]))
     _critic(layout, critic)
@@ -179,13 +118,7 @@ def log_prob_from_records(layout, rec, policy):
     records [W, T, Bm, F] (or [T, Bm, F]) or compact records [W, T + 1, Bm, Fc] (or [T + 1, Bm, Fc]) of `layout` -- obs and
     action sit at the same offsets in both -- -> [W, T, Bm] (or [T, Bm]); the tail row of compact records holds no action and
     is left out."""
-    Fc = getattr(layout, 'Fc', None)
-    if isinstance(rec, torch.Tensor) and Fc is not None and rec.shape[-1] == Fc and rec.dim() in (3, 4):
-        if rec.shape[-3] != layout.T + 1:
-            raise ValueError("compact records must hold %d rows of time (the tail included), got %d" % (layout.T + 1, rec.shape[-3]))
-        rec = rec[..., :layout.T, :, :]
-    else:
-        rec = _records(layout, rec, layout.F, 'records')
+    rec = columns(layout, rec)
     lp = torch.empty(rec.shape[:-1], dtype=rec.dtype, device=rec.device)
     evaluate_rows(policy, rec[..., layout.fields['obs']], rec[..., layout.fields['action']], logp=lp)
     return lp

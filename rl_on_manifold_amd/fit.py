@@ -25,10 +25,9 @@ nothing and can be captured in a graph.  No numerics here, and no fall-back: a m
 import torch
 
 from . import _lib_fit as _lf
-from .evaluate import _check_rows, _launches, _records
-from .returns import _overlap, _stream
+from ._rows import (buffers, carve, check_rows, checked_blocks, checked_idx, column, columns, fill, inputs, needs_gpu, no_overlap,
+                    one_launch, reuse, rows_of, run, sized)
 
-_DTYPES = {torch.float32: _lf.F32, torch.float64: _lf.F64}
 _HEADS = {_lf.VALUE: 'value', _lf.PPO_CLIP: 'PPO'}
 
 
@@ -43,17 +42,8 @@ class Gradients:
         self.flat = torch.empty(_lf.grad_size(n_in, n_out, head), dtype=dtype, device=device)
         self.stats = torch.empty(_lf.STATS, dtype=dtype, device=device)
         self.workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=device)
-        o = 0
-        for name, shape in (('W1', (64, n_in)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (n_out, 64)), ('b3', (n_out,)),
-                            ('log_std', (n_out,) if head == _lf.PPO_CLIP else None)):
-            if shape is None:
-                setattr(self, name, None)
-                continue
-            n = 1
-            for s in shape:
-                n *= s
-            setattr(self, name, self.flat[o:o + n].view(shape))
-            o += n
+        carve(self, self.flat, (('W1', (64, n_in)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (n_out, 64)), ('b3', (n_out,)),
+                                ('log_std', (n_out,) if head == _lf.PPO_CLIP else None)))
 
     @property
     def loss(self):
@@ -87,10 +77,7 @@ def check_idx(idx, n_rows):
 
 
 def _gradient(net, head, x, action, weight, logp_old, clip, idx, out, n_blocks):
-    if not isinstance(x, torch.Tensor) or x.dim() < 1:
-        raise ValueError("obs must be a tensor [..., n_in]")
-    if x.dtype not in _DTYPES:
-        raise ValueError("obs must be float32 or float64, got %s" % x.dtype)
+    lead = rows_of(x, 'obs')
     ppo = head == _lf.PPO_CLIP
     if ppo and net.tensors.get('std') is None:
         raise ValueError("the policy gradient needs a policy with std")
@@ -101,66 +88,31 @@ def _gradient(net, head, x, action, weight, logp_old, clip, idx, out, n_blocks):
         raise ValueError("obs has rows of %d where the network takes %d" % (x.shape[-1], m.n_in))
     if not ppo and m.n_out != 1:
         raise ValueError("the critic must map the %d observation elements to one value" % m.n_in)
-    lead = tuple(x.shape[:-1])
-    if any(n == 0 for n in lead):
-        raise ValueError("obs holds no rows: %s" % (tuple(x.shape),))
-    one = lambda t: t.unsqueeze(-1) if isinstance(t, torch.Tensor) else t           # noqa: E731
-    wname = 'adv' if ppo else 'target'
-    ts, slots, names = [_check_rows(x, 'obs', lead, m.n_in, x)], ['x'], ['obs']
+    rows = [('x', 'obs', x, m.n_in), ('weight', 'target', column(weight), 1)]
     if ppo:
-        ts.append(_check_rows(action, 'action', lead, m.n_out, x))
-        slots.append('action')
-        names.append('action')
-    ts.append(_check_rows(one(weight), wname, lead, 1, x))
-    slots.append('weight')
-    names.append(wname)
-    if ppo:
-        ts.append(_check_rows(one(logp_old), 'logp_old', lead, 1, x))
-        slots.append('logp_old')
-        names.append('logp_old')
-    launches = _launches(lead, [t.stride()[:-1] for t in ts])
-    if len(launches) != 1:
-        raise ValueError("the leading dimensions %s with strides %s do not collapse to one (outer, inner) pair: a gradient "
-                         "cannot be split over launches" % (lead, [t.stride()[:-1] for t in ts]))
-    offs, n_outer, n_inner, strides = launches[0]
-    if idx is not None:
-        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1:
-            raise ValueError("idx must be a one-dimensional int64 tensor of at least one row number")
-        if idx.device != x.device or not idx.is_contiguous():
-            raise ValueError("idx must be contiguous and on %s, got %s" % (x.device, idx.device))
-    if not 0 <= int(n_blocks) <= _lf.MAX_BLOCKS:
-        raise ValueError("n_blocks must be 0 (the library chooses) .. %d, got %d" % (_lf.MAX_BLOCKS, n_blocks))
-    if x.device.type != 'cuda':                        # the last check that needs no device: everything above is about shapes
-        raise ValueError("the kernels of libatacom_fit.so run on a GPU; got tensors on %s" % x.device)
+        rows = [rows[0], ('action', 'action', action, m.n_out), ('weight', 'adv', column(weight), 1),
+                ('logp_old', 'logp_old', column(logp_old), 1)]
+    slots, names, ts, _ = zip(*rows)
+    for _, name, t, width in rows:
+        check_rows(t, name, lead, width, x)
+    launch = one_launch(ts, names, lead, 'a gradient')
+    idx = checked_idx(idx, x)
+    n_blocks = checked_blocks(n_blocks, _lf.MAX_BLOCKS)
+    needs_gpu(x, 'fit')
     a = _lf.new_args()
-    a.device, a.dtype, a.n_blocks, a.head, a.net = x.device.index, _DTYPES[x.dtype], int(n_blocks), head, m
-    a.n_outer, a.n_inner, a.clip = n_outer, n_inner, float(clip)
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
+    fill(a, x, n_blocks, launch, slots, ts, idx)
+    a.head, a.net, a.clip = head, m, float(clip)
     lib = _lf.load()
-    need = lib.atacom_fit_workspace_size(a)
-    if need == 0:
-        _lf.check(_lf.E_INVALID)
+    need = sized(_lf, lib.atacom_fit_workspace_size(a))
     key = (m.n_in, m.n_out, head, x.dtype, x.device)
     if out is None:
         out = Gradients(m.n_in, m.n_out, head, x.dtype, x.device, need, key)
-    elif not isinstance(out, Gradients) or out.key != key:
-        raise ValueError("out must be the Gradients of a %s call for a %d -> %d network in %s on %s" % (
+    else:
+        reuse((out,), Gradients, key, need, lambda: "Gradients of a %s call for a %d -> %d network in %s on %s" % (
             _HEADS[head], m.n_in, m.n_out, x.dtype, x.device))
-    elif out.workspace.numel() < need:
-        raise ValueError("out was made for fewer workgroups: its workspace holds %d bytes where this call needs %d" % (
-            out.workspace.numel(), need))
-    for o, oname in ((out.flat, 'the gradients'), (out.stats, 'the statistics'), (out.workspace, 'the workspace')):
-        for t, name in list(zip(ts, names)) + ([(idx, 'idx')] if idx is not None else []):
-            if _overlap(o, t):
-                raise ValueError("%s overlap %s: the call does not work in place" % (oname, name))
-    size = x.element_size()
-    for t, s, off, (so, si) in zip(ts, slots, offs, strides):
-        setattr(a, s, _lf.View(t.data_ptr() + off * size, so, si))
+    no_overlap(buffers(out), inputs(ts, names, idx))
     a.grad, a.stats = out.flat.data_ptr(), out.stats.data_ptr()
-    a.workspace, a.workspace_bytes = out.workspace.data_ptr(), out.workspace.numel()
-    a.stream = _stream(x.device.index)
-    _lf.check(lib.atacom_fit_gradient(a))
+    run(a, lib.atacom_fit_gradient, _lf.check, x, out.workspace)
     return out
 
 
@@ -181,27 +133,16 @@ def policy_gradient(policy, obs, action, adv, logp_old, *, clip=0.2, idx=None, o
     return _gradient(policy, _lf.PPO_CLIP, obs, action, adv, logp_old, clip, idx, out, n_blocks)
 
 
-def _columns(layout, rec):
-    """Full records [W, T, Bm, F] (or [T, Bm, F]) or compact records [W, T + 1, Bm, Fc] (or [T + 1, Bm, Fc]), whose tail row
-    holds no action and is left out, as log_prob_from_records reads them."""
-    Fc = getattr(layout, 'Fc', None)
-    if isinstance(rec, torch.Tensor) and Fc is not None and rec.shape[-1] == Fc and rec.dim() in (3, 4):
-        if rec.shape[-3] != layout.T + 1:
-            raise ValueError("compact records must hold %d rows of time (the tail included), got %d" % (layout.T + 1, rec.shape[-3]))
-        return rec[..., :layout.T, :, :]
-    return _records(layout, rec, layout.F, 'records')
-
-
 def value_gradient_from_records(layout, rec, target, critic, *, idx=None, out=None):
     """value_gradient with the obs column of packed records of `layout` read in place; target [W, T, Bm] (or [T, Bm]), `idx`
     numbers the flat [W * T * Bm] rows."""
-    rec = _columns(layout, rec)
+    rec = columns(layout, rec)
     return value_gradient(critic, rec[..., layout.fields['obs']], target, idx=idx, out=out)
 
 
 def policy_gradient_from_records(layout, rec, adv, logp_old, policy, *, clip=0.2, idx=None, out=None):
     """policy_gradient with the obs and action columns of packed records of `layout` read in place; adv and logp_old
     [W, T, Bm] (or [T, Bm]), `idx` numbers the flat [W * T * Bm] rows."""
-    rec = _columns(layout, rec)
+    rec = columns(layout, rec)
     return policy_gradient(policy, rec[..., layout.fields['obs']], rec[..., layout.fields['action']], adv, logp_old, clip=clip,
                            idx=idx, out=out)

@@ -18,14 +18,13 @@ import torch
 
 from . import _lib_fit as _lf
 from . import _lib_offgrad as _lg
-from .evaluate import _check_rows
+from . import _rows
+from ._rows import (DTYPES, buffers, carve, check_rows, checked_blocks, checked_idx, fill, inputs, n_rows, needs_gpu, network_struct,
+                    no_overlap, one_launch, optional_rows, reuse, rows_of, run, sized)
 from .fit import Gradients
-from .offpolicy import QCritic, _idx, _one_launch, _rows_out
-from .returns import _overlap, _stream
+from .offpolicy import QCritic
 
-_DTYPES = {torch.float32: _lg.F32, torch.float64: _lg.F64}
 _KINDS = {'ddpg': _lg.DDPG, 'td3': _lg.TD3}
-_CRITIC_KEYS = ('W1', 'b1', 'W2', 'b2', 'W2a', 'W3', 'b3', 'obs_shift', 'obs_scale', 'act_scale')
 PARAMS = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'W2a')          # the order of QGradients.flat: that of _lib_offpolicy.PARAMS
 
 
@@ -39,14 +38,8 @@ class QGradients:
         self.flat = torch.empty(_lg.grad_size(n1, 1, n_act), dtype=dtype, device=device)
         self.stats = torch.empty(_lg.STATS, dtype=dtype, device=device)
         self.workspace = workspace
-        o = 0
-        for name, shape in (('W1', (64, n1)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (1, 64)), ('b3', (1,)),
-                            ('W2a', (64, n_act))):
-            n = 1
-            for s in shape:
-                n *= s
-            setattr(self, name, self.flat[o:o + n].view(shape))
-            o += n
+        carve(self, self.flat, (('W1', (64, n1)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (1, 64)), ('b3', (1,)),
+                                ('W2a', (64, n_act))))
 
     @property
     def loss(self):
@@ -66,23 +59,17 @@ class QGradients:
 
 
 def _critic_struct(critic, device, dtype):
-    """The atacom_offgrad_critic of a QCritic: its own ctypes struct, filled from QCritic.tensors like QCritic.as_struct_on (tensors
-    already on the device in the dtype are used as they are; the copies live as long as the critic or until the next call)."""
-    device = torch.device(device)
-    dev = {k: (None if v is None else torch.as_tensor(v).detach().to(device=device, dtype=dtype).contiguous())
-           for k, v in critic.tensors.items()}
-    critic._keep_offgrad = dev
-    D, k = critic.n_obs, critic.n_act
-    n1 = D + k if critic.kind == 'td3' else D
-    for name, shape in (('W1', (64, n1)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W2a', (64, k)), ('W3', (1, 64)),
-                        ('b3', (1,)), ('obs_shift', (D,)), ('obs_scale', (D,)), ('act_scale', (k,))):
-        if dev[name] is not None and tuple(dev[name].shape) != shape:
-            raise ValueError("%s has the shape %s where the critic needs %s" % (name, tuple(dev[name].shape), shape))
-    c = _lg.Critic()
-    c.kind, c.n_obs, c.n_act, c.activation = _KINDS[critic.kind], D, k, critic.activation
-    for name in _CRITIC_KEYS:
-        setattr(c, name, None if dev[name] is None else dev[name].data_ptr())
-    return c, n1
+    """The atacom_offgrad_critic of a QCritic: this library's own ctypes struct, filled like QCritic.as_struct_on; its copies
+    live beside those of the forward calls, as long as the critic or until the next gradient call."""
+    c = network_struct(critic, critic.shapes(), _lg.Critic, device, dtype, keep='_keep_offgrad')
+    c.kind, c.n_obs, c.n_act, c.activation = _KINDS[critic.kind], critic.n_obs, critic.n_act, critic.activation
+    return c
+
+
+def _fresh(n, need, key):
+    """n QGradients of `key` = (n1, k, dtype, device) on one workspace of `need` bytes."""
+    ws = torch.empty(need, dtype=torch.uint8, device=key[3])
+    return tuple(QGradients(*key, ws, key) for _ in range(n))
 
 
 def _sizes(critic):
@@ -93,28 +80,6 @@ def _sizes(critic):
     if n1 > _lg.MAX_IN:
         raise ValueError("n1 = %d first-layer inputs exceed %d" % (n1, _lg.MAX_IN))
     return D, k, n1
-
-
-def _checked_blocks(n_blocks):
-    if not isinstance(n_blocks, int) or not 0 <= n_blocks <= _lg.MAX_BLOCKS:
-        raise ValueError("n_blocks must be 0 (the library chooses) or 1 .. %d" % _lg.MAX_BLOCKS)
-    return n_blocks
-
-
-def _obs_checks(obs, what='obs'):
-    if not isinstance(obs, torch.Tensor) or obs.dim() < 1:
-        raise ValueError("%s must be a tensor [..., n]" % what)
-    if obs.dtype not in _DTYPES:
-        raise ValueError("%s must be float32 or float64, got %s" % (what, obs.dtype))
-    lead = tuple(obs.shape[:-1])
-    if any(n == 0 for n in lead) or not lead:
-        raise ValueError("%s holds no rows: %s" % (what, tuple(obs.shape)))
-    return lead
-
-
-def _needs_gpu(x):
-    if x.device.type != 'cuda':                            # the last check that needs no device
-        raise ValueError("the kernels of libatacom_offgrad.so run on a GPU; got tensors on %s" % x.device)
 
 
 def critic_gradient(critics, obs, action, target, *, idx=None, out=None, n_blocks=0):
@@ -132,53 +97,9 @@ def critic_gradient(critics, obs, action, target, *, idx=None, out=None, n_block
     if any((c.kind, c.n_obs, c.n_act) != (c0.kind, c0.n_obs, c0.n_act) for c in critics):
         raise ValueError("the two critics differ in kind, observation or action size")
     D, k, n1 = _sizes(c0)
-    lead = _obs_checks(obs)
-    ts = [_check_rows(obs, 'obs', lead, D, obs), _check_rows(action, 'action', lead, k, obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, ('obs', 'action'), lead)
-    idx = _idx(idx, obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
-    if not isinstance(target, torch.Tensor) or tuple(target.shape) != (M,):
-        raise ValueError("target must be a tensor of shape (%d,): one value per row of the call" % M)
-    if target.dtype != obs.dtype or target.device != obs.device:
-        raise ValueError("target must be a %s tensor on %s" % (obs.dtype, obs.device))
-    n_blocks = _checked_blocks(n_blocks)
-    _needs_gpu(obs)
-    lib = _lg.load()
-    need = lib.atacom_offgrad_workspace_size(_DTYPES[obs.dtype], len(critics), n1, 1, k, M, n_blocks)
-    if need == 0:
-        _lg.check(_lg.E_INVALID)
-    key = (n1, k, obs.dtype, obs.device)
-    if out is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=obs.device)
-        outs = tuple(QGradients(n1, k, obs.dtype, obs.device, ws, key) for _ in critics)
-    else:
-        outs = (out,) if isinstance(out, QGradients) else tuple(out)
-        if len(outs) != len(critics) or not all(isinstance(o, QGradients) and o.key == key for o in outs):
-            raise ValueError("out must be the QGradients (one per critic) of a call for critics of %d first-layer inputs and %d "
-                             "action elements in %s on %s" % (n1, k, obs.dtype, obs.device))
-        if outs[0].workspace.numel() < need:
-            raise ValueError("out was made for fewer workgroups: its workspace holds %d bytes where this call needs %d" % (
-                outs[0].workspace.numel(), need))
-    ins = list(zip(ts, ('obs', 'action'))) + [(target, 'target')] + ([(idx, 'idx')] if idx is not None else [])
-    for o in outs:
-        for buf, oname in ((o.flat, 'the gradients'), (o.stats, 'the statistics'), (outs[0].workspace, 'the workspace')):
-            for t, name in ins:
-                if _overlap(buf, t):
-                    raise ValueError("%s overlap %s: the call does not work in place" % (oname, name))
-    a = _lg.new_args(_lg.CriticArgs)
-    a.device, a.dtype, a.n_blocks, a.n_critics, a.n_outer, a.n_inner = obs.device.index, _DTYPES[obs.dtype], n_blocks, len(critics), n_outer, n_inner
-    for j, c in enumerate(critics):
-        a.critics[j] = _critic_struct(c, obs.device, obs.dtype)[0]
-        a.grad[j], a.stats[j] = outs[j].flat.data_ptr(), outs[j].stats.data_ptr()
-    size = obs.element_size()
-    a.obs = _lg.View(ts[0].data_ptr() + offs[0] * size, *strides[0])
-    a.action = _lg.View(ts[1].data_ptr() + offs[1] * size, *strides[1])
-    a.target, a.target_stride = target.data_ptr(), (target.stride(0) if M > 1 else 1)
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
-    a.workspace, a.workspace_bytes = outs[0].workspace.data_ptr(), outs[0].workspace.numel()
-    a.stream = _stream(obs.device.index)
-    _lg.check(lib.atacom_offgrad_critic_gradient(a))
+    outs = _rows.critic_gradient(_lg, 'offgrad', critics, (D, k), obs, action, target, idx, out, n_blocks, (
+        QGradients, (n1, k), (n1, 1, k), _fresh, _critic_struct,
+        "QGradients (one per critic) of a call for critics of %d first-layer inputs and %d action elements" % (n1, k)))
     return outs[0] if single else outs
 
 
@@ -197,48 +118,28 @@ def actor_gradient(actor, critic, obs, *, idx=None, out=None, action_out=None, d
     if (int(W1.shape[1]), int(W3.shape[0])) != (D, k):
         raise ValueError("the actor maps %d to %d where the critic takes %d observation and %d action elements" % (
             W1.shape[1], W3.shape[0], D, k))
-    lead = _obs_checks(obs)
-    ts = [_check_rows(obs, 'obs', lead, D, obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, ('obs',), lead)
-    idx = _idx(idx, obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
-    n_blocks = _checked_blocks(n_blocks)
-    _needs_gpu(obs)
+    lead = rows_of(obs, 'obs')
+    ts = [check_rows(obs, 'obs', lead, D, obs)]
+    launch = one_launch(ts, ('obs',), lead)
+    idx = checked_idx(idx, obs)
+    M = n_rows(idx, launch)
+    n_blocks = checked_blocks(n_blocks, _lg.MAX_BLOCKS)
+    needs_gpu(obs, 'offgrad')
     lib = _lg.load()
-    need = lib.atacom_offgrad_workspace_size(_DTYPES[obs.dtype], 1, D, k, 0, M, n_blocks)
-    if need == 0:
-        _lg.check(_lg.E_INVALID)
+    need = sized(_lg, lib.atacom_offgrad_workspace_size(DTYPES[obs.dtype], 1, D, k, 0, M, n_blocks))
     key = (D, k, _lf.VALUE, obs.dtype, obs.device)
     if out is None:
         out = Gradients(D, k, _lf.VALUE, obs.dtype, obs.device, need, key)
-    elif not isinstance(out, Gradients) or out.key != key:
-        raise ValueError("out must be the Gradients of an actor_gradient call for a %d -> %d network in %s on %s" % (D, k, obs.dtype, obs.device))
-    elif out.workspace.numel() < need:
-        raise ValueError("out was made for fewer workgroups: its workspace holds %d bytes where this call needs %d" % (
-            out.workspace.numel(), need))
+    else:
+        reuse((out,), Gradients, key, need, lambda: "Gradients of an actor_gradient call for a %d -> %d network in %s on %s" % (
+            D, k, obs.dtype, obs.device))
     a = _lg.new_args(_lg.ActorArgs)
-    outs = [(out.flat, 'the gradients'), (out.stats, 'the statistics'), (out.workspace, 'the workspace')]
-    if action_out is not None:
-        action_out, a.action_out_stride = _rows_out(action_out, 'action_out', M, k, obs)
-        a.action_out = action_out.data_ptr()
-        outs.append((action_out, 'action_out'))
-    if dqda_out is not None:
-        dqda_out, a.dqda_out_stride = _rows_out(dqda_out, 'dqda_out', M, k, obs)
-        a.dqda_out = dqda_out.data_ptr()
-        outs.append((dqda_out, 'dqda_out'))
-    ins = [(ts[0], 'obs')] + ([(idx, 'idx')] if idx is not None else [])
-    for o, oname in outs:
-        for t, name in ins + [p for p in outs if p[0] is not o]:
-            if _overlap(o, t):
-                raise ValueError("%s overlap %s: the call does not work in place" % (oname, name))
-    a.device, a.dtype, a.n_blocks, a.n_outer, a.n_inner = obs.device.index, _DTYPES[obs.dtype], n_blocks, n_outer, n_inner
+    outs = buffers(out)
+    optional_rows(a, outs, obs, M, [('action_out', action_out, k), ('dqda_out', dqda_out, k)])
+    no_overlap(outs, inputs(ts, ('obs',), idx))
+    fill(a, obs, n_blocks, launch, ('obs',), ts, idx)
     a.actor = actor.as_struct_on(obs.device, obs.dtype)
-    a.critic = _critic_struct(critic, obs.device, obs.dtype)[0]
-    a.obs = _lg.View(ts[0].data_ptr() + offs[0] * obs.element_size(), *strides[0])
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
+    a.critic = _critic_struct(critic, obs.device, obs.dtype)
     a.grad, a.stats = out.flat.data_ptr(), out.stats.data_ptr()
-    a.workspace, a.workspace_bytes = out.workspace.data_ptr(), out.workspace.numel()
-    a.stream = _stream(obs.device.index)
-    _lg.check(lib.atacom_offgrad_actor_gradient(a))
+    run(a, lib.atacom_offgrad_actor_gradient, _lg.check, obs, out.workspace)
     return out

@@ -11,13 +11,11 @@ only: nothing here is differentiable.  No numerics here, and no fall-back: a mis
 import torch
 
 from . import _lib_offpolicy as _lo
-from .evaluate import _check_rows, _launches
-from .returns import _overlap, _stream
+from ._rows import (DTYPES, TARGET_ROWS, bound, check_rows, checked_blocks, checked_idx, fill, inputs, n_rows, needs_gpu, network_struct,
+                    no_overlap, one_launch, optional_rows, rows_of, rows_out, run, target_rows)
 from .rollout import pack_fields, record_columns, record_fields
 
-_DTYPES = {torch.float32: _lo.F32, torch.float64: _lo.F64}
 _KINDS = {'ddpg': _lo.DDPG, 'td3': _lo.TD3}
-_CRITIC_KEYS = ('W1', 'b1', 'W2', 'b2', 'W2a', 'W3', 'b3', 'obs_shift', 'obs_scale', 'act_scale')
 
 
 class QCritic:
@@ -66,70 +64,18 @@ class QCritic:
                    net._h2_a.weight.detach(), net._h3.weight.detach(), net._h3.bias.detach(), kind=kind, act_scale=s,
                    obs_shift=shift, obs_scale=scale, activation=activation)
 
+    def shapes(self):
+        """((name, shape), ...) of the tensors, in the order of the library's struct."""
+        D, k = self.n_obs, self.n_act
+        return (('W1', (64, D + k if self.kind == 'td3' else D)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W2a', (64, k)),
+                ('W3', (1, 64)), ('b3', (1,)), ('obs_shift', (D,)), ('obs_scale', (D,)), ('act_scale', (k,)))
+
     def as_struct_on(self, device, dtype):
         """The atacom_offpolicy_critic of this network on `device` in `dtype`.  Tensors that are already there are used as they
         are (no copy, so the call can be captured in a graph); the copies live as long as the critic or until the next call."""
-        device = torch.device(device)
-        dev = {k: (None if v is None else torch.as_tensor(v).detach().to(device=device, dtype=dtype).contiguous())
-               for k, v in self.tensors.items()}
-        self._keep = dev
-        D, k = self.n_obs, self.n_act
-        n1 = D + k if self.kind == 'td3' else D
-        for name, shape in (('W1', (64, n1)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W2a', (64, k)), ('W3', (1, 64)),
-                            ('b3', (1,)), ('obs_shift', (D,)), ('obs_scale', (D,)), ('act_scale', (k,))):
-            if dev[name] is not None and tuple(dev[name].shape) != shape:
-                raise ValueError("%s has the shape %s where the critic needs %s" % (name, tuple(dev[name].shape), shape))
-        c = _lo.Critic()
-        c.kind, c.n_obs, c.n_act, c.activation = _KINDS[self.kind], D, k, self.activation
-        for name in _CRITIC_KEYS:
-            setattr(c, name, None if dev[name] is None else dev[name].data_ptr())
+        c = network_struct(self, self.shapes(), _lo.Critic, device, dtype)
+        c.kind, c.n_obs, c.n_act, c.activation = _KINDS[self.kind], self.n_obs, self.n_act, self.activation
         return c
-
-
-def _device_checks(x, what):
-    if not isinstance(x, torch.Tensor) or x.dim() < 1:
-        raise ValueError("%s must be a tensor [..., n]" % what)
-    if x.device.type != 'cuda':
-        raise ValueError("the kernels of libatacom_offpolicy.so run on a GPU; got tensors on %s" % x.device)
-    if x.dtype not in _DTYPES:
-        raise ValueError("%s must be float32 or float64, got %s" % (what, x.dtype))
-
-
-def _one_launch(ts, names, lead):
-    launches = _launches(lead, [t.stride()[:-1] for t in ts])
-    if len(launches) != 1:
-        raise ValueError("the leading dimensions %s of %s do not collapse to one (outer, inner) pair" % (tuple(lead), ', '.join(names)))
-    return launches[0]
-
-
-def _idx(idx, x):
-    if idx is None:
-        return None
-    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1:
-        raise ValueError("idx must be a one-dimensional int64 tensor of at least one row number")
-    if idx.device != x.device or not idx.is_contiguous():
-        raise ValueError("idx must be contiguous and on %s" % x.device)
-    return idx
-
-
-def _rows_out(t, name, M, width, x):
-    """An output (or eps) of M rows of `width`: [M, width] (or [M] for width 1) with contiguous rows -> (tensor, row stride)."""
-    shape = (M, width) if width > 1 or (isinstance(t, torch.Tensor) and t.dim() == 2) else (M,)
-    if t is None:
-        t = torch.empty(shape, dtype=x.dtype, device=x.device)
-    if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
-        raise ValueError("%s must be a tensor of shape %s" % (name, shape))
-    if t.dtype != x.dtype or t.device != x.device:
-        raise ValueError("%s must be a %s tensor on %s" % (name, x.dtype, x.device))
-    if t.dim() == 2 and width > 1 and t.stride(1) != 1:
-        raise ValueError("the %d elements of a row of %s must be contiguous" % (width, name))
-    return t, (t.stride(0) if M > 1 else width)
-
-
-def _n_blocks(n_blocks):
-    if not isinstance(n_blocks, int) or not 0 <= n_blocks <= _lo.MAX_BLOCKS:
-        raise ValueError("n_blocks must be 0 (the library chooses) or 1 .. %d" % _lo.MAX_BLOCKS)
-    return n_blocks
 
 
 def q_values(critic, obs, action, *, idx=None, out=None, n_blocks=0):
@@ -138,41 +84,21 @@ def q_values(critic, obs, action, *, idx=None, out=None, n_blocks=0):
     numbers, repeats allowed; the library does not guard one out of range), or every row in order without idx."""
     if not isinstance(critic, QCritic):
         raise ValueError("critic must be a QCritic")
-    _device_checks(obs, 'obs')
-    lead = tuple(obs.shape[:-1])
-    if any(n == 0 for n in lead) or not lead:
-        raise ValueError("obs holds no rows: %s" % (tuple(obs.shape),))
-    ts = [_check_rows(obs, 'obs', lead, critic.n_obs, obs), _check_rows(action, 'action', lead, critic.n_act, obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, ('obs', 'action'), lead)
-    idx = _idx(idx, obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
-    q, q_stride = _rows_out(out, 'out', M, 1, obs)
-    for t, name in zip(ts, ('obs', 'action')):
-        if _overlap(q, t):
-            raise ValueError("out overlaps %s: the call does not work in place" % name)
+    lead = rows_of(obs, 'obs')
+    names = ('obs', 'action')
+    ts = [check_rows(obs, 'obs', lead, critic.n_obs, obs), check_rows(action, 'action', lead, critic.n_act, obs)]
+    launch = one_launch(ts, names, lead)
+    idx = checked_idx(idx, obs)
+    q, q_stride = rows_out(out, 'out', n_rows(idx, launch), 1, obs)
+    no_overlap([(q, 'out')], inputs(ts, names))
+    n_blocks = checked_blocks(n_blocks, _lo.MAX_BLOCKS)
+    needs_gpu(obs, 'offpolicy')
     a = _lo.new_args(_lo.QArgs)
-    a.device, a.dtype, a.n_blocks, a.n_outer, a.n_inner = obs.device.index, _DTYPES[obs.dtype], _n_blocks(n_blocks), n_outer, n_inner
+    fill(a, obs, n_blocks, launch, names, ts, idx)
     a.critic = critic.as_struct_on(obs.device, obs.dtype)
-    size = obs.element_size()
-    a.obs = _lo.View(ts[0].data_ptr() + offs[0] * size, *strides[0])
-    a.action = _lo.View(ts[1].data_ptr() + offs[1] * size, *strides[1])
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
-    a.q, a.q_stride, a.stream = q.data_ptr(), q_stride, _stream(obs.device.index)
-    _lo.check(_lo.load().atacom_offpolicy_q(a))
+    a.q, a.q_stride = q.data_ptr(), q_stride
+    run(a, _lo.load().atacom_offpolicy_q, _lo.check, obs)
     return q
-
-
-def _bound(v, k, x, name):
-    """A scalar, a sequence or a tensor -> [k] on the device of x in its dtype; a tensor already there is used as it is."""
-    if isinstance(v, torch.Tensor) and v.device == x.device and v.dtype == x.dtype and tuple(v.shape) == (k,) and v.is_contiguous():
-        return v
-    t = torch.as_tensor(v, dtype=torch.float64).detach().reshape(-1)
-    if t.numel() == 1:
-        t = t.expand(k)
-    if t.numel() != k:
-        raise ValueError("%s: expected a scalar or %d values, got %d" % (name, k, t.numel()))
-    return t.to(device=x.device, dtype=x.dtype).contiguous()
 
 
 def td_target(actor, critics, next_obs, reward, absorbing, gamma, *, eps=None, noise_std=0.0, noise_clip=0.0, low=None, high=None,
@@ -186,7 +112,7 @@ def td_target(actor, critics, next_obs, reward, absorbing, gamma, *, eps=None, n
     `actor` is an MlpPolicy (its exploration settings are not read), `critics` one QCritic or a pair, eps [M, k] standard normals
     of the caller (row r belongs to row r of the call, not to idx[r]; None: no noise), low / high the bounds of the action (both
     or neither).  -> y [M]; action_out [M, k], if given, receives a''."""
-    _device_checks(next_obs, 'next_obs')
+    lead = rows_of(next_obs, 'next_obs')
     critics = (critics,) if isinstance(critics, QCritic) else tuple(critics)
     if len(critics) not in (1, 2) or not all(isinstance(c, QCritic) for c in critics):
         raise ValueError("critics must be one QCritic or a pair of them")
@@ -201,53 +127,27 @@ def td_target(actor, critics, next_obs, reward, absorbing, gamma, *, eps=None, n
     if float(gamma) != float(gamma) or abs(float(gamma)) == float('inf'):
         raise ValueError("gamma must be finite, got %r" % (gamma,))
     D, k = c0.n_obs, c0.n_act
-    lead = tuple(next_obs.shape[:-1])
-    if any(n == 0 for n in lead) or not lead:
-        raise ValueError("next_obs holds no rows: %s" % (tuple(next_obs.shape),))
-    if isinstance(absorbing, torch.Tensor) and absorbing.dtype == torch.bool:
-        absorbing = absorbing.to(next_obs.dtype)
-    one = lambda t: t.unsqueeze(-1) if isinstance(t, torch.Tensor) else t           # noqa: E731
-    names = ('next_obs', 'reward', 'absorbing')
-    ts = [_check_rows(next_obs, 'next_obs', lead, D, next_obs), _check_rows(one(reward), 'reward', lead, 1, next_obs),
-          _check_rows(one(absorbing), 'absorbing', lead, 1, next_obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, names, lead)
-    idx = _idx(idx, next_obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
+    ts, launch, idx, M = target_rows(next_obs, reward, absorbing, lead, D, idx)
     m = actor.as_struct_on(next_obs.device, next_obs.dtype)
     if (m.n_in, m.n_out) != (D, k):
         raise ValueError("the actor maps %d to %d where the critics take %d observation and %d action elements" % (m.n_in, m.n_out, D, k))
-    y, y_stride = _rows_out(out, 'out', M, 1, next_obs)
-    ins = list(zip(ts, names))
     a = _lo.new_args(_lo.TargetArgs)
-    keep = []
-    if eps is not None:
-        eps, a.eps_stride = _rows_out(eps, 'eps', M, k, next_obs)
-        a.eps = eps.data_ptr()
-        ins.append((eps, 'eps'))
-    outs = [(y, 'out')]
-    if action_out is not None:
-        action_out, a.action_out_stride = _rows_out(action_out, 'action_out', M, k, next_obs)
-        a.action_out = action_out.data_ptr()
-        outs.append((action_out, 'action_out'))
-    for o, oname in outs:
-        for t, name in ins + [p for p in outs if p[0] is not o]:
-            if _overlap(o, t):
-                raise ValueError("%s overlaps %s: the call does not work in place" % (oname, name))
+    y, a.y_stride = rows_out(out, 'out', M, 1, next_obs)
+    ins, outs = inputs(ts, TARGET_ROWS), [(y, 'out')]
+    optional_rows(a, ins, next_obs, M, [('eps', eps, k)])
+    optional_rows(a, outs, next_obs, M, [('action_out', action_out, k)])
+    no_overlap(outs, ins)
     if low is not None:
-        keep = [_bound(low, k, next_obs, 'low'), _bound(high, k, next_obs, 'high')]
+        keep = [bound(low, k, next_obs, 'low'), bound(high, k, next_obs, 'high')]
         a.act_low, a.act_high = keep[0].data_ptr(), keep[1].data_ptr()
-    a.device, a.dtype, a.n_blocks, a.n_outer, a.n_inner = next_obs.device.index, _DTYPES[next_obs.dtype], _n_blocks(n_blocks), n_outer, n_inner
+    n_blocks = checked_blocks(n_blocks, _lo.MAX_BLOCKS)
+    needs_gpu(next_obs, 'offpolicy')
+    fill(a, next_obs, n_blocks, launch, TARGET_ROWS, ts, idx)
     a.n_critics, a.actor = len(critics), m
     for j, c in enumerate(critics):
         a.critics[j] = c.as_struct_on(next_obs.device, next_obs.dtype)
-    size = next_obs.element_size()
-    for t, name, off, st in zip(ts, names, offs, strides):
-        setattr(a, name, _lo.View(t.data_ptr() + off * size, *st))
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
-    a.noise_std, a.noise_clip, a.gamma = float(noise_std), float(noise_clip), float(gamma)
-    a.y, a.y_stride, a.stream = y.data_ptr(), y_stride, _stream(next_obs.device.index)
-    _lo.check(_lo.load().atacom_offpolicy_target(a))
+    a.noise_std, a.noise_clip, a.gamma, a.y = float(noise_std), float(noise_clip), float(gamma), y.data_ptr()
+    run(a, _lo.load().atacom_offpolicy_target, _lo.check, next_obs)
     return y
 
 
@@ -288,17 +188,15 @@ def soft_update(targets, onlines, tau):
             raise ValueError("pair %d: the target and the online set differ in shape" % j)
         for t in tt + ot:
             ref = t if ref is None else ref
-            if t.device.type != 'cuda':
-                raise ValueError("the kernels of libatacom_offpolicy.so run on a GPU; got tensors on %s" % t.device)
-            if t.dtype not in _DTYPES or t.dtype != ref.dtype or t.device != ref.device or not t.is_contiguous():
+            if t.dtype not in DTYPES or t.dtype != ref.dtype or t.device != ref.device or not t.is_contiguous():
                 raise ValueError("the tensors of a soft update are contiguous, on one device and all float32 or all float64")
         p = a.pairs[j]
         p.n_in, p.n_out, p.n_act = shape_t
         for i, (t, o) in enumerate(zip(tt, ot)):
             p.target[i], p.online[i] = t.data_ptr(), o.data_ptr()
-    a.device, a.dtype, a.n_pairs, a.tau = ref.device.index, _DTYPES[ref.dtype], len(targets), float(tau)
-    a.stream = _stream(ref.device.index)
-    _lo.check(_lo.load().atacom_offpolicy_soft_update(a))
+    needs_gpu(ref, 'offpolicy')
+    a.device, a.dtype, a.n_pairs, a.tau = ref.device.index, DTYPES[ref.dtype], len(targets), float(tau)
+    run(a, _lo.load().atacom_offpolicy_soft_update, _lo.check, ref)
 
 
 class ReplayMemory:

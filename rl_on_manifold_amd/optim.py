@@ -20,7 +20,7 @@ import torch
 from . import _lib_fit as _lf
 from . import _lib_optim as _lo
 from . import fit as _fit
-from .returns import _stream
+from ._rows import columns, stream
 
 _DTYPES = {torch.float32: _lo.F32, torch.float64: _lo.F64}
 _KEYS = ('net', 'log_std', 'std', 'scale', 'lr')
@@ -133,7 +133,7 @@ class Adam:
         a = self._args
         for s in a.groups:
             s.grad = None                                    # init reads no gradient and accepts none
-        a.stream = _stream(a.device)
+        a.stream = stream(a.device)
         _lo.check(self._lib.atacom_optim_adam_init(a))
 
     def step(self, *grads):
@@ -146,7 +146,7 @@ class Adam:
                 raise ValueError("grads[%d] must be the Gradients of a %s call for a %d -> %d network in %s on %s" % (
                     k, 'PPO' if g['log_std'] is not None else 'value', g['n_in'], g['n_out'], self.dtype, self.device))
             s.grad = gr.flat.data_ptr()
-        a.stream = _stream(a.device)
+        a.stream = stream(a.device)
         _lo.check(self._lib.atacom_optim_adam_step(a))
 
     def steps(self):
@@ -199,7 +199,7 @@ class GraphedUpdate:
         if not isinstance(optimizer, Adam) or len(optimizer.groups) != 2 or optimizer.groups[0]['net'] is not policy or \
                 optimizer.groups[1]['net'] is not critic:
             raise ValueError("optimizer must be an Adam of two groups: the policy's, then the critic's")
-        cols = _fit._columns(layout, rec)
+        cols = columns(layout, rec)
         n = 1
         for s in cols.shape[:-1]:
             n *= s

@@ -12,17 +12,11 @@ here, and no fall-back: a missing library is an error.
 import torch
 
 from . import _lib_returns as _lr
-from ._device_env import _raw_stream
+from ._rows import overlap, stream
 from .rollout import record_columns
 
 _DTYPES = {torch.float32: _lr.F32, torch.float64: _lr.F64}
 _sizes_cache = {}
-
-
-def _stream(index):
-    if _raw_stream is not None:
-        return _raw_stream(index)
-    return torch.cuda.current_stream(torch.device('cuda', index)).cuda_stream
 
 
 def _three(x, name, shape=None):
@@ -82,21 +76,6 @@ def _sizes(sizes, W, Bm, device):
     return t, t.data_ptr()
 
 
-def _extent(x):
-    """[first byte, one past the last byte) of the memory a strided tensor touches."""
-    lo = hi = 0
-    for n, st in zip(x.shape, x.stride()):
-        if n == 0:
-            return x.data_ptr(), x.data_ptr()
-        lo, hi = lo + min(0, (n - 1) * st), hi + max(0, (n - 1) * st)
-    return x.data_ptr() + lo * x.element_size(), x.data_ptr() + (hi + 1) * x.element_size()
-
-
-def _overlap(a, b):
-    (a0, a1), (b0, b1) = _extent(a), _extent(b)
-    return a0 < b1 and b0 < a1
-
-
 def _shape(reward, flag_kind, sizes_ptr):
     if reward.device.type != 'cuda':
         raise ValueError("the kernels of libatacom_returns.so run on a GPU; got tensors on %s" % reward.device)
@@ -147,17 +126,17 @@ def compute_gae(reward, absorbing, last, v, v_next, gamma, lam, *, sizes=None, n
                 raise ValueError("out must be two contiguous %s tensors of shape %s on %s" % (r.dtype, tuple(shape_in), r.device))
         # a lane loads several steps ahead of the step it stores: an output laid over an input (or over the other output) would
         # be read after it was written
-        if _overlap(ret, adv):
+        if overlap(ret, adv):
             raise ValueError("out must be two tensors that do not overlap")
         for name, x in (('reward', r), ('absorbing', ab), ('last', la), ('v', v), ('v_next', v_next)):
-            if x is not None and (_overlap(ret, x) or _overlap(adv, x)):
+            if x is not None and (overlap(ret, x) or overlap(adv, x)):
                 raise ValueError("out overlaps %s: the call does not work in place" % name)
     a.ret, a.adv = _view(_three(ret, 'out[0]')), _view(_three(adv, 'out[1]'))
     stats = ws = None
     if normalize:
         ws, stats = _workspace(r), torch.empty((3,), dtype=torch.float64, device=r.device)
         a.d_workspace, a.d_stats = ws.data_ptr(), stats.data_ptr()
-    a.stream = _stream(r.device.index)
+    a.stream = stream(r.device.index)
     _lr.check(_lr.load().atacom_returns_gae(a))
     return (ret, adv, stats) if normalize else (ret, adv)
 
@@ -171,7 +150,7 @@ def normalize_advantages(adv, *, sizes=None):
     a.shape = _shape(x, _lr.FLAG_U8, sizes_ptr)
     a.adv = _view(x)
     ws, stats = _workspace(x), torch.empty((3,), dtype=torch.float64, device=x.device)
-    a.d_workspace, a.d_stats, a.stream = ws.data_ptr(), stats.data_ptr(), _stream(x.device.index)
+    a.d_workspace, a.d_stats, a.stream = ws.data_ptr(), stats.data_ptr(), stream(x.device.index)
     _lr.check(_lr.load().atacom_returns_normalize(a))
     return stats
 
@@ -187,7 +166,7 @@ def episode_returns(reward, last, gamma=1.0, *, sizes=None):
     a.gamma = float(gamma)
     a.reward, a.last = _view(r), _view(la)
     ws, res = _workspace(r), torch.empty((3,), dtype=torch.float64, device=r.device)
-    a.d_workspace, a.d_result, a.stream = ws.data_ptr(), res.data_ptr(), _stream(r.device.index)
+    a.d_workspace, a.d_result, a.stream = ws.data_ptr(), res.data_ptr(), stream(r.device.index)
     _lr.check(_lr.load().atacom_returns_episodes(a))
     return res
 

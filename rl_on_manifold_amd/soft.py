@@ -21,13 +21,10 @@ import torch
 
 from . import _lib_fit as _lf
 from . import _lib_soft as _ls
-from .evaluate import _check_rows
+from . import _rows
+from ._rows import (DTYPES, TARGET_ROWS, bound, check_rows, checked_blocks, checked_idx, fill, inputs, n_rows, needs_gpu, network_struct,
+                    no_overlap, one_launch, optional_rows, reuse, rows_of, rows_out, run, sized, stream, target_rows)
 from .fit import Gradients
-from .offpolicy import _bound, _idx, _one_launch, _rows_out
-from .returns import _overlap, _stream
-
-_DTYPES = {torch.float32: _ls.F32, torch.float64: _ls.F64}
-_CRITIC_KEYS = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'obs_shift', 'obs_scale')
 
 
 class SoftCritic:
@@ -67,19 +64,10 @@ class SoftCritic:
     def as_struct_on(self, device, dtype):
         """The atacom_soft_critic of this network on `device` in `dtype`.  Tensors that are already there are used as they are (no
         copy, so the call can be captured in a graph); the copies live as long as the critic or until the next call."""
-        device = torch.device(device)
-        dev = {k: (None if v is None else torch.as_tensor(v).detach().to(device=device, dtype=dtype).contiguous())
-               for k, v in self.tensors.items()}
-        self._keep = dev
         D, k = self.n_obs, self.n_act
-        for name, shape in (('W1', (64, D + k)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (1, 64)), ('b3', (1,)),
-                            ('obs_shift', (D,)), ('obs_scale', (D,))):
-            if dev[name] is not None and tuple(dev[name].shape) != shape:
-                raise ValueError("%s has the shape %s where the critic needs %s" % (name, tuple(dev[name].shape), shape))
-        c = _ls.Critic()
+        c = network_struct(self, (('W1', (64, D + k)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (1, 64)), ('b3', (1,)),
+                                  ('obs_shift', (D,)), ('obs_scale', (D,))), _ls.Critic, device, dtype)
         c.n_obs, c.n_act, c.activation = D, k, self.activation
-        for name in _CRITIC_KEYS:
-            setattr(c, name, None if dev[name] is None else dev[name].data_ptr())
         return c
 
 
@@ -90,6 +78,7 @@ class ActorGradients:
 
     def __init__(self, mu, sigma):
         self.mu, self.sigma, self.stats = mu, sigma, mu.stats
+        self.key, self.workspace = mu.key, mu.workspace               # what the rule of `out=` reads
 
     @property
     def loss(self):
@@ -116,28 +105,6 @@ def _sizes(c):
     return D, k
 
 
-def _checked_blocks(n_blocks):
-    if not isinstance(n_blocks, int) or not 0 <= n_blocks <= _ls.MAX_BLOCKS:
-        raise ValueError("n_blocks must be 0 (the library chooses) or 1 .. %d" % _ls.MAX_BLOCKS)
-    return n_blocks
-
-
-def _obs_checks(obs, what='obs'):
-    if not isinstance(obs, torch.Tensor) or obs.dim() < 1:
-        raise ValueError("%s must be a tensor [..., n]" % what)
-    if obs.dtype not in _DTYPES:
-        raise ValueError("%s must be float32 or float64, got %s" % (what, obs.dtype))
-    lead = tuple(obs.shape[:-1])
-    if any(n == 0 for n in lead) or not lead:
-        raise ValueError("%s holds no rows: %s" % (what, tuple(obs.shape)))
-    return lead
-
-
-def _needs_gpu(x):
-    if x.device.type != 'cuda':                            # the last check that needs no device
-        raise ValueError("the kernels of libatacom_soft.so run on a GPU; got tensors on %s" % x.device)
-
-
 def _policy_checks(policy, D, k):
     from .engine import MlpPolicy
     if not isinstance(policy, MlpPolicy):
@@ -160,23 +127,15 @@ def _squash_args(a, keep, x, k, M, eps, log_alpha, act_scale, act_shift, ins):
     """eps, log_alpha, act_scale and act_shift of a call into its argument struct; the tensors join `ins` and `keep`."""
     if eps is None:
         raise ValueError("eps must be a tensor of shape (%d, %d): the caller draws the standard normals" % (M, k))
-    eps, a.eps_stride = _rows_out(eps, 'eps', M, k, x)
-    a.eps = eps.data_ptr()
+    optional_rows(a, ins, x, M, [('eps', eps, k)])
     a.log_alpha = _log_alpha(log_alpha, x).data_ptr()
-    ins += [(eps, 'eps'), (log_alpha, 'log_alpha')]
+    ins.append((log_alpha, 'log_alpha'))
     for name, v in (('act_scale', act_scale), ('act_shift', act_shift)):
         if v is not None:
-            t = _bound(v, k, x, name)
+            t = bound(v, k, x, name)
             keep.append(t)
             setattr(a, name, t.data_ptr())
             ins.append((t, name))
-
-
-def _no_overlap(outs, ins):
-    for o, oname in outs:
-        for t, name in ins + [p for p in outs if p[0] is not o]:
-            if _overlap(o, t):
-                raise ValueError("%s overlaps %s: the call does not work in place" % (oname, name))
 
 
 def soft_td_target(policy, critics, next_obs, reward, absorbing, gamma, log_alpha, eps, *, act_scale=None, act_shift=None, idx=None,
@@ -193,46 +152,31 @@ def soft_td_target(policy, critics, next_obs, reward, absorbing, gamma, log_alph
     critics = _pair(critics)
     D, k = _sizes(critics[0])
     _policy_checks(policy, D, k)
-    lead = _obs_checks(next_obs, 'next_obs')
+    lead = rows_of(next_obs, 'next_obs')
     if float(gamma) != float(gamma) or abs(float(gamma)) == float('inf'):
         raise ValueError("gamma must be finite, got %r" % (gamma,))
-    if isinstance(absorbing, torch.Tensor) and absorbing.dtype == torch.bool:
-        absorbing = absorbing.to(next_obs.dtype)
-    one = lambda t: t.unsqueeze(-1) if isinstance(t, torch.Tensor) else t           # noqa: E731
-    names = ('next_obs', 'reward', 'absorbing')
-    ts = [_check_rows(next_obs, 'next_obs', lead, D, next_obs), _check_rows(one(reward), 'reward', lead, 1, next_obs),
-          _check_rows(one(absorbing), 'absorbing', lead, 1, next_obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, names, lead)
-    idx = _idx(idx, next_obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
-    n_blocks = _checked_blocks(n_blocks)
+    ts, launch, idx, M = target_rows(next_obs, reward, absorbing, lead, D, idx)
+    n_blocks = checked_blocks(n_blocks, _ls.MAX_BLOCKS)
     a = _ls.new_args(_ls.TargetArgs)
-    keep, ins = [], list(zip(ts, names)) + ([(idx, 'idx')] if idx is not None else [])
+    keep, ins = [], inputs(ts, TARGET_ROWS, idx)
     _squash_args(a, keep, next_obs, k, M, eps, log_alpha, act_scale, act_shift, ins)
-    y, a.y_stride = _rows_out(out, 'out', M, 1, next_obs)
+    y, a.y_stride = rows_out(out, 'out', M, 1, next_obs)
     outs = [(y, 'out')]
-    if action_out is not None:
-        action_out, a.action_out_stride = _rows_out(action_out, 'action_out', M, k, next_obs)
-        a.action_out = action_out.data_ptr()
-        outs.append((action_out, 'action_out'))
-    if logp_out is not None:
-        logp_out, a.logp_out_stride = _rows_out(logp_out, 'logp_out', M, 1, next_obs)
-        a.logp_out = logp_out.data_ptr()
-        outs.append((logp_out, 'logp_out'))
-    _no_overlap(outs, ins)
-    _needs_gpu(next_obs)
-    a.device, a.dtype, a.n_blocks, a.n_critics, a.n_outer, a.n_inner = next_obs.device.index, _DTYPES[next_obs.dtype], n_blocks, 2, n_outer, n_inner
-    a.policy = policy.as_struct_on(next_obs.device, next_obs.dtype)
+    optional_rows(a, outs, next_obs, M, [('action_out', action_out, k), ('logp_out', logp_out, 1)])
+    no_overlap(outs, ins)
+    needs_gpu(next_obs, 'soft')
+    fill(a, next_obs, n_blocks, launch, TARGET_ROWS, ts, idx)
+    a.n_critics, a.policy = 2, policy.as_struct_on(next_obs.device, next_obs.dtype)
     for j, c in enumerate(critics):
         a.critics[j] = c.as_struct_on(next_obs.device, next_obs.dtype)
-    size = next_obs.element_size()
-    for t, name, off, st in zip(ts, names, offs, strides):
-        setattr(a, name, _ls.View(t.data_ptr() + off * size, *st))
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
-    a.gamma, a.y, a.stream = float(gamma), y.data_ptr(), _stream(next_obs.device.index)
-    _ls.check(_ls.load().atacom_soft_target(a))
+    a.gamma, a.y = float(gamma), y.data_ptr()
+    run(a, _ls.load().atacom_soft_target, _ls.check, next_obs)
     return y
+
+
+def _fresh(n, need, key):
+    """n fit.Gradients of `key` = (n1, 1, the value head, dtype, device); the first holds the workspace of `need` bytes."""
+    return tuple(Gradients(*key, need if j == 0 else 0, key) for j in range(n))
 
 
 def soft_critic_gradient(critics, obs, action, target, *, idx=None, out=None, n_blocks=0):
@@ -244,52 +188,9 @@ def soft_critic_gradient(critics, obs, action, target, *, idx=None, out=None, n_
     single = isinstance(critics, SoftCritic)
     critics = (critics,) if single else _pair(critics)
     D, k = _sizes(critics[0])
-    n1 = D + k
-    lead = _obs_checks(obs)
-    ts = [_check_rows(obs, 'obs', lead, D, obs), _check_rows(action, 'action', lead, k, obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, ('obs', 'action'), lead)
-    idx = _idx(idx, obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
-    if not isinstance(target, torch.Tensor) or tuple(target.shape) != (M,):
-        raise ValueError("target must be a tensor of shape (%d,): one value per row of the call" % M)
-    if target.dtype != obs.dtype or target.device != obs.device:
-        raise ValueError("target must be a %s tensor on %s" % (obs.dtype, obs.device))
-    n_blocks = _checked_blocks(n_blocks)
-    _needs_gpu(obs)
-    lib = _ls.load()
-    need = lib.atacom_soft_workspace_size(_DTYPES[obs.dtype], len(critics), n1, 1, M, n_blocks)
-    if need == 0:
-        _ls.check(_ls.E_INVALID)
-    key = (n1, 1, _lf.VALUE, obs.dtype, obs.device)
-    if out is None:
-        outs = tuple(Gradients(n1, 1, _lf.VALUE, obs.dtype, obs.device, need if j == 0 else 0, key) for j in range(len(critics)))
-    else:
-        outs = (out,) if isinstance(out, Gradients) else tuple(out)
-        if len(outs) != len(critics) or not all(isinstance(o, Gradients) and o.key == key for o in outs):
-            raise ValueError("out must be the Gradients (one per critic) of a soft_critic_gradient call for critics of %d first-layer "
-                             "inputs in %s on %s" % (n1, obs.dtype, obs.device))
-        if outs[0].workspace.numel() < need:
-            raise ValueError("out was made for fewer workgroups: its workspace holds %d bytes where this call needs %d" % (
-                outs[0].workspace.numel(), need))
-    ins = list(zip(ts, ('obs', 'action'))) + [(target, 'target')] + ([(idx, 'idx')] if idx is not None else [])
-    bufs = [(outs[0].workspace, 'the workspace')]
-    for o in outs:
-        bufs += [(o.flat, 'the gradients'), (o.stats, 'the statistics')]
-    _no_overlap(bufs, ins)
-    a = _ls.new_args(_ls.CriticArgs)
-    a.device, a.dtype, a.n_blocks, a.n_critics, a.n_outer, a.n_inner = obs.device.index, _DTYPES[obs.dtype], n_blocks, len(critics), n_outer, n_inner
-    for j, c in enumerate(critics):
-        a.critics[j] = c.as_struct_on(obs.device, obs.dtype)
-        a.grad[j], a.stats[j] = outs[j].flat.data_ptr(), outs[j].stats.data_ptr()
-    size = obs.element_size()
-    a.obs = _ls.View(ts[0].data_ptr() + offs[0] * size, *strides[0])
-    a.action = _ls.View(ts[1].data_ptr() + offs[1] * size, *strides[1])
-    a.target, a.target_stride = target.data_ptr(), (target.stride(0) if M > 1 else 1)
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
-    a.workspace, a.workspace_bytes = outs[0].workspace.data_ptr(), outs[0].workspace.numel()
-    a.stream = _stream(obs.device.index)
-    _ls.check(lib.atacom_soft_critic_gradient(a))
+    outs = _rows.critic_gradient(_ls, 'soft', critics, (D, k), obs, action, target, idx, out, n_blocks, (
+        Gradients, (D + k, 1, _lf.VALUE), (D + k, 1), _fresh, SoftCritic.as_struct_on,
+        "Gradients (one per critic) of a soft_critic_gradient call for critics of %d first-layer inputs" % (D + k)))
     return outs[0] if single else outs
 
 
@@ -303,52 +204,37 @@ def soft_actor_gradient(policy, critics, obs, eps, log_alpha, target_entropy, *,
     critics = _pair(critics)
     D, k = _sizes(critics[0])
     _policy_checks(policy, D, k)
-    lead = _obs_checks(obs)
+    lead = rows_of(obs, 'obs')
     te = float(target_entropy)
     if te != te or abs(te) == float('inf'):
         raise ValueError("target_entropy must be finite, got %r" % (target_entropy,))
-    ts = [_check_rows(obs, 'obs', lead, D, obs)]
-    offs, n_outer, n_inner, strides = _one_launch(ts, ('obs',), lead)
-    idx = _idx(idx, obs)
-    M = idx.numel() if idx is not None else n_outer * n_inner
-    n_blocks = _checked_blocks(n_blocks)
+    ts = [check_rows(obs, 'obs', lead, D, obs)]
+    launch = one_launch(ts, ('obs',), lead)
+    idx = checked_idx(idx, obs)
+    M = n_rows(idx, launch)
+    n_blocks = checked_blocks(n_blocks, _ls.MAX_BLOCKS)
     a = _ls.new_args(_ls.ActorArgs)
-    keep, ins = [], [(ts[0], 'obs')] + ([(idx, 'idx')] if idx is not None else [])
+    keep, ins = [], inputs(ts, ('obs',), idx)
     _squash_args(a, keep, obs, k, M, eps, log_alpha, act_scale, act_shift, ins)
-    _needs_gpu(obs)
+    needs_gpu(obs, 'soft')
     lib = _ls.load()
-    need = lib.atacom_soft_workspace_size(_DTYPES[obs.dtype], 2, D, k, M, n_blocks)
-    if need == 0:
-        _ls.check(_ls.E_INVALID)
+    need = sized(_ls, lib.atacom_soft_workspace_size(DTYPES[obs.dtype], 2, D, k, M, n_blocks))
     key = (D, k, _lf.VALUE, obs.dtype, obs.device)
     if out is None:
-        out = ActorGradients(Gradients(D, k, _lf.VALUE, obs.dtype, obs.device, need, key), Gradients(D, k, _lf.VALUE, obs.dtype, obs.device, 0, key))
-    elif not isinstance(out, ActorGradients) or out.mu.key != key:
-        raise ValueError("out must be the ActorGradients of a soft_actor_gradient call for a %d -> %d policy in %s on %s" % (D, k, obs.dtype, obs.device))
-    elif out.mu.workspace.numel() < need:
-        raise ValueError("out was made for fewer workgroups: its workspace holds %d bytes where this call needs %d" % (
-            out.mu.workspace.numel(), need))
-    outs = [(out.mu.flat, 'the gradients of mu'), (out.sigma.flat, 'the gradients of sigma'), (out.stats, 'the statistics'),
-            (out.mu.workspace, 'the workspace')]
-    for name, t, width in (('action_out', action_out, k), ('logp_out', logp_out, 1), ('q_out', q_out, 2), ('dqda_out', dqda_out, k)):
-        if t is not None:
-            t, stride = _rows_out(t, name, M, width, obs)
-            setattr(a, name, t.data_ptr())
-            setattr(a, name + '_stride', stride)
-            outs.append((t, name))
-    _no_overlap(outs, ins)
-    a.device, a.dtype, a.n_blocks, a.n_outer, a.n_inner = obs.device.index, _DTYPES[obs.dtype], n_blocks, n_outer, n_inner
+        out = ActorGradients(*_fresh(2, need, key))
+    else:
+        reuse((out,), ActorGradients, key, need, lambda: "ActorGradients of a soft_actor_gradient call for a %d -> %d policy in %s on %s" % (
+            D, k, obs.dtype, obs.device))
+    outs = [(out.mu.flat, 'out.mu.flat'), (out.sigma.flat, 'out.sigma.flat'), (out.stats, 'out.stats'), (out.workspace, 'out.workspace')]
+    optional_rows(a, outs, obs, M, [('action_out', action_out, k), ('logp_out', logp_out, 1), ('q_out', q_out, 2), ('dqda_out', dqda_out, k)])
+    no_overlap(outs, ins)
+    fill(a, obs, n_blocks, launch, ('obs',), ts, idx)
     a.policy = policy.as_struct_on(obs.device, obs.dtype)
     for j, c in enumerate(critics):
         a.critics[j] = c.as_struct_on(obs.device, obs.dtype)
-    a.obs = _ls.View(ts[0].data_ptr() + offs[0] * obs.element_size(), *strides[0])
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
     a.target_entropy = te
     a.grad_mu, a.grad_sigma, a.stats = out.mu.flat.data_ptr(), out.sigma.flat.data_ptr(), out.stats.data_ptr()
-    a.workspace, a.workspace_bytes = out.mu.workspace.data_ptr(), out.mu.workspace.numel()
-    a.stream = _stream(obs.device.index)
-    _ls.check(lib.atacom_soft_actor_gradient(a))
+    run(a, lib.atacom_soft_actor_gradient, _ls.check, obs, out.workspace)
     return out
 
 
@@ -358,7 +244,7 @@ class AlphaAdam:
     the gradient from a one-value device tensor (ActorGradients.alpha_grad) -- the host reads nothing."""
 
     def __init__(self, log_alpha, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
-        if not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1 or log_alpha.dtype not in _DTYPES or not log_alpha.is_contiguous():
+        if not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1 or log_alpha.dtype not in DTYPES or not log_alpha.is_contiguous():
             raise ValueError("log_alpha must be a contiguous tensor of one float32 or float64 value")
         if not (isinstance(betas, (list, tuple)) and len(betas) == 2 and all(0.0 <= float(b) < 1.0 for b in betas)):
             raise ValueError("betas must be two numbers in [0, 1), got %r" % (betas,))
@@ -366,7 +252,7 @@ class AlphaAdam:
             raise ValueError("lr must be >= 0 and finite, got %r" % (lr,))
         if not float(eps) > 0.0 or float(eps) == float('inf'):
             raise ValueError("eps must be > 0 and finite, got %r" % (eps,))
-        _needs_gpu(log_alpha)
+        needs_gpu(log_alpha, 'soft')
         self.log_alpha, self.lr, self.betas, self.eps = log_alpha.detach(), float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.state = torch.zeros(_ls.ALPHA_STATE, dtype=torch.uint8, device=log_alpha.device)
         self.step_count = self.state[:8].view(torch.int64)
@@ -384,10 +270,10 @@ class AlphaAdam:
         if not isinstance(grad, torch.Tensor) or grad.numel() != 1 or grad.dtype != self.log_alpha.dtype or grad.device != self.log_alpha.device:
             raise ValueError("grad must be a tensor of one %s value on %s" % (self.log_alpha.dtype, self.log_alpha.device))
         a = _ls.new_args(_ls.AlphaArgs)
-        a.device, a.dtype = self.log_alpha.device.index, _DTYPES[self.log_alpha.dtype]
+        a.device, a.dtype = self.log_alpha.device.index, DTYPES[self.log_alpha.dtype]
         a.log_alpha, a.grad, a.state = self.log_alpha.data_ptr(), grad.data_ptr(), self.state.data_ptr()
         a.lr, a.beta1, a.beta2, a.eps = self.lr, self.betas[0], self.betas[1], self.eps
-        a.stream = _stream(a.device)
+        a.stream = stream(a.device)
         _ls.check(self._lib.atacom_soft_alpha_step(a))
 
     def snapshot(self):

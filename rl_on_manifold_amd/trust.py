@@ -29,10 +29,10 @@ import torch
 
 from . import _lib_trust as _lt
 from . import fit as _fit
-from .evaluate import _check_rows, _launches, evaluate_rows
-from .returns import _overlap, _stream
+from ._rows import (carve, check_rows, checked_blocks, checked_idx, columns, fill, inputs, needs_gpu, no_overlap, one_launch, reuse,
+                    rows_of, run, sized)
+from .evaluate import evaluate_rows
 
-_DTYPES = {torch.float32: _lt.F32, torch.float64: _lt.F64}
 _NAMES = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3')
 BIG_CLIP = 1e30        # PPO's clip at which no row is inactive: 1 - clip and 1 + clip are finite in float32, and rho >= 0
 
@@ -40,14 +40,6 @@ BIG_CLIP = 1e30        # PPO's clip at which no row is inactive: 1 - clip and 1 
 def _shapes(n_in, n_out):
     return (('W1', (64, n_in)), ('b1', (64,)), ('W2', (64, 64)), ('b2', (64,)), ('W3', (n_out, 64)), ('b3', (n_out,)),
             ('log_std', (n_out,)))
-
-
-def _views(obj, flat, n_in, n_out):
-    o = 0
-    for name, shape in _shapes(n_in, n_out):
-        n = math.prod(shape)
-        setattr(obj, name, flat[o:o + n].view(shape))
-        o += n
 
 
 class FisherProduct:
@@ -59,7 +51,7 @@ class FisherProduct:
         self.n_in, self.n_out, self.key = n_in, n_out, key
         self.flat = torch.empty(_lt.size(n_in, n_out), dtype=dtype, device=device)
         self.workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=device)
-        _views(self, self.flat, n_in, n_out)
+        carve(self, self.flat, _shapes(n_in, n_out))
 
     @classmethod
     def like(cls, policy, obs, *, idx=None, n_blocks=0):
@@ -67,10 +59,7 @@ class FisherProduct:
 
 
 def _product(policy, x, v, damping, idx, out, n_blocks, make_only=False):
-    if not isinstance(x, torch.Tensor) or x.dim() < 1:
-        raise ValueError("obs must be a tensor [..., n_in]")
-    if x.dtype not in _DTYPES:
-        raise ValueError("obs must be float32 or float64, got %s" % x.dtype)
+    lead = rows_of(x, 'obs')
     if policy.tensors.get('std') is None:
         raise ValueError("the Fisher-vector product needs a policy with std")
     if not (isinstance(damping, (int, float)) and math.isfinite(damping) and damping >= 0.0):
@@ -78,59 +67,35 @@ def _product(policy, x, v, damping, idx, out, n_blocks, make_only=False):
     m = policy.as_struct_on(x.device, x.dtype)
     if x.shape[-1] != m.n_in:
         raise ValueError("obs has rows of %d where the network takes %d" % (x.shape[-1], m.n_in))
-    lead = tuple(x.shape[:-1])
-    if any(n == 0 for n in lead):
-        raise ValueError("obs holds no rows: %s" % (tuple(x.shape),))
-    _check_rows(x, 'obs', lead, m.n_in, x)
+    check_rows(x, 'obs', lead, m.n_in, x)
     n_all = _lt.size(m.n_in, m.n_out)
     if not make_only:
         if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.numel() != n_all:
             raise ValueError("v must be a one-dimensional tensor of %d values (P + n_out of a %d -> %d policy)" % (n_all, m.n_in, m.n_out))
         if v.dtype != x.dtype or v.device != x.device or not v.is_contiguous():
             raise ValueError("v must be contiguous, %s and on %s, got %s on %s" % (x.dtype, x.device, v.dtype, v.device))
-    launches = _launches(lead, [x.stride()[:-1]])
-    if len(launches) != 1:
-        raise ValueError("the leading dimensions %s with strides %s do not collapse to one (outer, inner) pair: a product "
-                         "cannot be split over launches" % (lead, x.stride()[:-1]))
-    offs, n_outer, n_inner, strides = launches[0]
-    if idx is not None:
-        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1:
-            raise ValueError("idx must be a one-dimensional int64 tensor of at least one row number")
-        if idx.device != x.device or not idx.is_contiguous():
-            raise ValueError("idx must be contiguous and on %s, got %s" % (x.device, idx.device))
-    if not 0 <= int(n_blocks) <= _lt.MAX_BLOCKS:
-        raise ValueError("n_blocks must be 0 (the library chooses) .. %d, got %d" % (_lt.MAX_BLOCKS, n_blocks))
+    launch = one_launch((x,), ('obs',), lead, 'a product')
+    idx = checked_idx(idx, x)
+    n_blocks = checked_blocks(n_blocks, _lt.MAX_BLOCKS)
     key = (m.n_in, m.n_out, x.dtype, x.device)
-    if out is not None and (not isinstance(out, FisherProduct) or out.key != key):
-        raise ValueError("out must be the FisherProduct of a call for a %d -> %d policy in %s on %s" % (m.n_in, m.n_out, x.dtype, x.device))
-    if x.device.type != 'cuda':                        # the last check that needs no device: everything above is about shapes
-        raise ValueError("the kernels of libatacom_trust.so run on a GPU; got tensors on %s" % x.device)
+    describe = lambda: "FisherProduct of a call for a %d -> %d policy in %s on %s" % (m.n_in, m.n_out, x.dtype, x.device)  # noqa: E731
+    if out is not None:
+        reuse((out,), FisherProduct, key, 0, describe)        # whose it is needs no device; what it holds needs the library
+    needs_gpu(x, 'trust')
     a = _lt.new_args()
-    a.device, a.dtype, a.n_blocks, a.net = x.device.index, _DTYPES[x.dtype], int(n_blocks), m
-    a.n_outer, a.n_inner, a.damping = n_outer, n_inner, float(damping)
-    if idx is not None:
-        a.idx, a.n_idx = idx.data_ptr(), idx.numel()
+    fill(a, x, n_blocks, launch, ('x',), (x,), idx)
+    a.net, a.damping = m, float(damping)
     lib = _lt.load()
-    need = lib.atacom_trust_workspace_size(a)
-    if need == 0:
-        _lt.check(_lt.E_INVALID)
+    need = sized(_lt, lib.atacom_trust_workspace_size(a))
     if out is None:
         out = FisherProduct(m.n_in, m.n_out, x.dtype, x.device, need, key)
-    elif out.workspace.numel() < need:
-        raise ValueError("out was made for fewer workgroups: its workspace holds %d bytes where this call needs %d" % (
-            out.workspace.numel(), need))
+    else:
+        reuse((out,), FisherProduct, key, need, describe)
     if make_only:
         return out
-    for o, oname in ((out.flat, 'the product'), (out.workspace, 'the workspace')):
-        for t, name in [(x, 'obs'), (v, 'v')] + ([(idx, 'idx')] if idx is not None else []):
-            if _overlap(o, t):
-                raise ValueError("%s overlaps %s: the call does not work in place" % (oname, name))
-    (so, si), = strides
-    a.x = _lt.View(x.data_ptr() + offs[0] * x.element_size(), so, si)
+    no_overlap([(out.flat, 'out.flat'), (out.workspace, 'out.workspace')], inputs((x, v), ('obs', 'v'), idx))
     a.v, a.out = v.data_ptr(), out.flat.data_ptr()
-    a.workspace, a.workspace_bytes = out.workspace.data_ptr(), out.workspace.numel()
-    a.stream = _stream(x.device.index)
-    _lt.check(lib.atacom_trust_fvp(a))
+    run(a, lib.atacom_trust_fvp, _lt.check, x, out.workspace)
     return out
 
 
@@ -147,7 +112,7 @@ def fisher_vector_product(policy, obs, v, *, damping=0.0, idx=None, out=None, n_
 def fisher_vector_product_from_records(layout, rec, v, policy, *, damping=0.0, idx=None, out=None, n_blocks=0):
     """fisher_vector_product with the obs column of full or compact packed records of `layout` read in place (the tail row of
     compact records is left out); `idx` numbers the flat [W * T * Bm] rows."""
-    rec = _fit._columns(layout, rec)
+    rec = columns(layout, rec)
     return fisher_vector_product(policy, rec[..., layout.fields['obs']], v, damping=damping, idx=idx, out=out, n_blocks=n_blocks)
 
 
@@ -232,7 +197,7 @@ def trpo_step(layout, rec, adv, logp_old, policy, log_std, *, max_kl=1e-2, ent_c
     The candidates are written into policy.tensors and `log_std` in place, and exp(log_std) into policy.tensors['std']; if none
     is accepted everything is restored bit for bit.  -> dict(loss_old, loss_new, kl, halvings, accepted, cg_residual); rejected:
     loss_new = loss_old, kl = 0, halvings = line_search.  One read-back per candidate, as the reference."""
-    cols = _fit._columns(layout, rec)
+    cols = columns(layout, rec)
     if not isinstance(line_search, int) or line_search < 1:
         raise ValueError("line_search must be an integer >= 1, got %r" % (line_search,))
     if not (isinstance(max_kl, (int, float)) and max_kl > 0.0 and math.isfinite(max_kl)):

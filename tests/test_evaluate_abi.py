@@ -158,41 +158,20 @@ def test_python_arguments_are_refused_before_the_library_is_called():
     for call, words in ((lambda: evaluate.evaluate_mlp(pol, x), 'run on a GPU'),
                         (lambda: evaluate.evaluate_mlp(pol, 3.0), r'\[\.\.\., n_in\]'),
                         (lambda: evaluate.gaussian_log_prob(pol, x, act), 'run on a GPU'),
-                        (lambda: evaluate.evaluate_rows(pol, x), 'run on a GPU'),
+                        (lambda: evaluate.evaluate_rows(pol, x, y=act.clone()), 'run on a GPU'),
+                        (lambda: evaluate.evaluate_rows(pol, x), 'nothing to compute'),
                         (lambda: evaluate.values_from_records(lay, torch.zeros(3, 5, lay.F + 1), critic), 'full records must be'),
                         (lambda: evaluate.values_from_records(lay, torch.zeros(3, 5, lay.F), pol), 'to one value'),
                         (lambda: evaluate.values_from_compact(clay, torch.zeros(3, 5, clay.Fc), None, None, critic), 'rows of time'),
                         (lambda: evaluate.log_prob_from_records(clay, torch.zeros(3, 5, 7), pol), 'records must be')):
         with pytest.raises(ValueError, match=words):
             call()
-    # the rules every tensor of a call is held to
-    for t, name, width, words in ((torch.zeros(3, 5, 3), 'x', 4, 'shape'), (x.double(), 'action', 4, 'must be a torch.float32 tensor'),
-                                  (torch.zeros(3, 5, 8)[..., ::2], 'y', 4, 'must be contiguous')):
-        with pytest.raises(ValueError, match=words):
-            evaluate._check_rows(t, name, (3, 5), width, x)
     ddpg = MlpPolicy(*lin(64, 4), *lin(64, 64), *lin(2, 64), std=torch.ones(2))
     ddpg.explore = 2
     with pytest.raises(ValueError, match='DDPG'):
         ddpg.as_struct_on('cpu', torch.float32)
     m = pol.as_struct_on('cpu', torch.float64)                       # the sibling of as_struct needs no environment
     assert (m.n_in, m.hidden, m.n_out, m.activation) == (4, 64, 2, 0) and m.std and not m.obs_shift and not m.sW1
-
-
-def test_strided_views_become_at_most_two_dimensions_per_launch():
-    """evaluate._launches: what is handed to the library for the shapes the module meets."""
-    from rl_on_manifold_amd.evaluate import _launches
-    F = 13
-    # [T, B] columns of records with a padded batch stride, next to a contiguous output
-    assert _launches((3, 5), [(8 * F, F), (5, 1)]) == [([0, 0], 3, 5, [(8 * F, F), (5, 1)])]
-    # contiguous: one dimension
-    assert _launches((3, 5), [(5 * F, F), (5, 1)]) == [([0, 0], 1, 15, [(0, F), (0, 1)])]
-    # [W, T, Bm] of gathered records: W and T merge
-    assert _launches((2, 3, 5), [(24 * F, 8 * F, F), (15, 5, 1)]) == [([0, 0], 6, 5, [(8 * F, F), (5, 1)])]
-    # nothing merges: the first dimension is walked, one launch per index
-    got = _launches((2, 3, 5), [(100 * F, 8 * F, F), (15, 5, 1)])
-    assert got == [([0, 0], 3, 5, [(8 * F, F), (5, 1)]), ([100 * F, 15], 3, 5, [(8 * F, F), (5, 1)])]
-    assert _launches((1, 1), [(7, 7), (1, 1)]) == [([0, 0], 1, 1, [(0, 0), (0, 0)])]
-    assert _launches((), [(), ()]) == [([0, 0], 1, 1, [(0, 0), (0, 0)])]
 
 
 @abi.needs_llvm('llvm-readelf')

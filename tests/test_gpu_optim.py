@@ -73,7 +73,7 @@ class Raw:
             self.groups.append(g)
 
     def args(self, which, lr=oo.LR):
-        from rl_on_manifold_amd.returns import _stream
+        from rl_on_manifold_amd._rows import stream as _stream
         lo = self.lo
         a = lo.new_args()
         a.device, a.dtype, a.n_groups = 0, lo.F32 if self.dt == 'f32' else lo.F64, len(which)
