@@ -220,13 +220,18 @@ int atacom_soft_critic_gradient(const atacom_soft_critic_args* args);
 
 /* The gradient of  L = mean_r (alpha * logp - min_j Q_j([xn | a]))  with respect to the six tensors of the mu network and the six
  * of the sigma network; the critics are only read.  Per row, after the row arithmetic above, each line individually rounded:
- *     q = q_2 < q_1 ? q_2 : q_1                        (equal values: critic 1)
+ *     q = q_2 < q_1 ? q_2 : q_1                        (equal values: critic 1.  The reference's torch.min splits the gradient
+ *                                                       0.5 / 0.5 between the critics at an exact tie; the device does not, by
+ *                                                       design: tests/test_edge_cases_oracle.py shows the difference)
  *     delta2 = W3^T * act'(h2),  delta1 = (W2^T delta2) * act'(h1)  of that critic, from dq = 1
  *     dq/da = the a-columns of W1^T delta1
  *     r = (2 t) * w;   r = r / e                        (= d(-c)/du: c = log(w + 1e-6), dw/du = -2 t w)
  *     du = alpha * r - dq/da * (act_scale * w)
  *     dm = du
  *     dl = (du * p - alpha) * [log_std_min < l_raw < log_std_max]
+ *                                                      (strict on both sides.  The reference's torch.clamp passes the gradient
+ *                                                       where l_raw equals a bound exactly; the device gives dl = 0 there, by
+ *                                                       design: tests/test_edge_cases_oracle.py shows the difference)
  * then the backward pass of Mu from dm and of Sig from dl as in atacom_soft_critic_gradient, the sums divided by M at the end.
  * stats[0] = L = mean_r (alpha logp - q), stats[1] = mean_r logp, stats[2] = mean_r -(logp + target_entropy) (the gradient of
  * MushroomRL's alpha loss with respect to log_alpha), stats[3] = the share of rows with an element of l clamped.

@@ -63,10 +63,24 @@ def forward(net, x):
     return out
 
 
-def _act_prime(h, e_h, act):
-    """(act', its bound) from the activation's value."""
+def _units(exempt, layer):
+    """The units of hidden layer `layer` (1 or 2) among the engineered (layer, unit) pairs `exempt` (tests/edge_cases.py)."""
+    return [] if exempt is None else [int(u) for l, u in exempt if l == layer]
+
+
+def _kink(a, e, exempt=None, layer=0, factor=1.0):
+    """Per row: a pre-activation within factor * its bound of 0, the engineered units of `exempt` left out."""
+    at = np.abs(a) <= factor * e
+    at[:, _units(exempt, layer)] = False
+    return at.any(1)
+
+
+def _act_prime(h, e_h, act, open_units=()):
+    """(act', its bound) from the activation's value.  open_units: the units whose gate reads h >= 0 (wrong='kink_open')."""
     if act == 'relu':
-        return (h > 0.0).astype(np.float64), np.zeros_like(h)
+        ap = (h > 0.0).astype(np.float64)
+        ap[:, list(open_units)] = (h[:, list(open_units)] >= 0.0)
+        return ap, np.zeros_like(h)
     return 1.0 - h * h, 2.0 * np.abs(h) * e_h + e_h * e_h + gamma(2) * (1.0 + h * h)
 
 
@@ -89,12 +103,15 @@ def _wgrad(d, e_d, A_d, S_d, h, e_h, M):
     return val, e, scale
 
 
-def gradient(net, x, head, weight, action=None, std=None, logp_old=None, clip=0.2, idx=None):
+def gradient(net, x, head, weight, action=None, std=None, logp_old=None, clip=0.2, idx=None, exempt=None, wrong=None):
     """The call of atacom_fit_gradient on rows x [R, n_in] (gathered through idx, if given) -> dict:
     flat, bound, scale: [P (+ n_out)] in the library's order (bound: float32, per element; scale: the backward pass on absolute
         values, what a float64 evaluation is measured against);
     stats, stats_bound, stats_scale: [4];  kinks: the number of rows the bound does not cover (module docstring);
-    parts: {name: (value, bound, scale)} of the same numbers by tensor;  inactive: [M] bool (PPO)."""
+    parts: {name: (value, bound, scale)} of the same numbers by tensor;  inactive: [M] bool (PPO).
+    exempt: the engineered (layer, unit) pairs of tests/edge_cases.py, left out of `kinks`; nothing else is.
+    wrong='kink_open': the gate of those units reads h >= 0."""
+    assert wrong in (None, 'kink_open')
     x, w = _f64(x), _f64(weight)
     act = net.get('activation', 'relu')
     if idx is not None:
@@ -108,7 +125,7 @@ def gradient(net, x, head, weight, action=None, std=None, logp_old=None, clip=0.
     W2, W3 = _f64(net['W2']), _f64(net['W3'])
     kink = np.zeros(M, bool)
     if act == 'relu':
-        kink |= (np.abs(f['a1']) <= SAFETY * f['e_a1']).any(1) | (np.abs(f['a2']) <= SAFETY * f['e_a2']).any(1)
+        kink |= _kink(f['a1'], f['e_a1'], exempt, 1, SAFETY) | _kink(f['a2'], f['e_a2'], exempt, 2, SAFETY)
     n_out = y.shape[1]
     ls = e_ls = np.zeros((M, n_out))
     inactive = np.zeros(M, bool)
@@ -152,8 +169,9 @@ def gradient(net, x, head, weight, action=None, std=None, logp_old=None, clip=0.
         e_st = np.stack([np.abs(w) * e_rho + gamma(2) * np.abs(term), np.zeros(M), e_lp + U32 * np.abs(arg)], 1)
         a_st = np.stack([np.abs(term), inactive.astype(np.float64), np.abs(lpo) + np.abs(z * z).sum(-1) * 0.5 + const], 1)
     # ---- backward, with the same pass on absolute values next to it
-    ap2, e_ap2 = _act_prime(f['h2'], f['e_h2'], act)
-    ap1, e_ap1 = _act_prime(f['h1'], f['e_h1'], act)
+    opn = exempt if wrong == 'kink_open' else None
+    ap2, e_ap2 = _act_prime(f['h2'], f['e_h2'], act, _units(opn, 2))
+    ap1, e_ap1 = _act_prime(f['h1'], f['e_h1'], act, _units(opn, 1))
     A_dy = np.abs(dy)
     da2, e_da2 = _back(W3, dy, e_dy, ap2, e_ap2, 8)
     A_da2 = (A_dy @ np.abs(W3)) * np.abs(ap2)
@@ -209,15 +227,20 @@ def _cases():
 CASES = _cases()
 
 
-def case(seed, head, n_in, n_out, activation, normalise, rows, dtype=np.float32, check=True):
+def case(seed, head, n_in, n_out, activation, normalise, rows, dtype=np.float32, check=True, edge=None):
     """A case in `dtype`: dict(net, x, action, std, weight, logp_old, clip).  VALUE: targets at y + N(0, 1).  PPO: advantages
     N(0, 1); logp_old placed so that rho spans [0.5, 2]; std log-uniform in [1e-2, 2] (evaluate_oracle.case_data) and actions
     out to six standard deviations where the bound allows it (below).  With 64 rows or more a PPO batch holds inactive rows on each side and
     active rows of both signs.  The seed is moved on, deterministically, until no row sits at a kink (zero exclusions); `check`
-    asserts what the docstring promises."""
+    asserts what the docstring promises.  edge: a construction of tests/edge_cases.py, edge(net, x) -> the engineered
+    (layer, unit) pairs; it changes net and x in place before anything is derived from them, and its units alone are left out of
+    the count (c['exempt'])."""
+    exempt = None
     for attempt in range(64):
         s = seed + 1000 * attempt
         net, x, action, std = case_data(s, n_in, n_out, activation, normalise, rows, dtype)
+        if edge is not None:
+            exempt = edge(net, x)
         rng = np.random.default_rng(s + 77)
         if head == VALUE:
             weight = (forward(net, x)['y'][:, 0] + rng.normal(0.0, 1.0, rows)).astype(dtype)
@@ -248,6 +271,7 @@ def case(seed, head, n_in, n_out, activation, normalise, rows, dtype=np.float32,
             lpo = (logp - log_rho).astype(dtype)
             weight = rng.normal(0.0, 1.0, rows).astype(dtype)
             c = dict(net=net, x=x, action=action, std=std, weight=weight, logp_old=lpo, clip=CLIP)
+        c['exempt'] = exempt
         want = oracle(c, head)
         if want['kinks'] == 0:
             break
@@ -262,5 +286,5 @@ def case(seed, head, n_in, n_out, activation, normalise, rows, dtype=np.float32,
     return c
 
 
-def oracle(c, head, idx=None):
-    return gradient(c['net'], c['x'], head, c['weight'], c['action'], c['std'], c['logp_old'], c['clip'], idx)
+def oracle(c, head, idx=None, wrong=None):
+    return gradient(c['net'], c['x'], head, c['weight'], c['action'], c['std'], c['logp_old'], c['clip'], idx, c.get('exempt'), wrong)

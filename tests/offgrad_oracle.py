@@ -30,7 +30,7 @@ import functools
 import numpy as np
 
 from evaluate_oracle import SAFETY, TANH_ABS, U32, gamma
-from fit_oracle import _act_prime, _back, _wgrad
+from fit_oracle import _act_prime, _back, _kink, _units, _wgrad
 import offpolicy_oracle as oo
 from offpolicy_oracle import DDPG, TD3, _f64, _hidden, _layer, _normalise
 
@@ -44,8 +44,16 @@ def _k(n, offset):
     return int(SAFETY * (n + offset)) - offset
 
 
-def critic_forward(c, x, a, e_a=None):
-    """critic_q's chain with everything a backward pass needs: x1, as, h1, h2, q (and e_*), mag_q, the pre-activations a1, a2."""
+def _of(exempt, key, j=None):
+    """The engineered (layer, unit) pairs of one network from a case's description {'actor': pairs, 'critics': [pairs, pairs], ...}
+    (tests/edge_cases.py); None where there is none."""
+    v = None if exempt is None else exempt.get(key)
+    return v if v is None or j is None else v[j]
+
+
+def critic_forward(c, x, a, e_a=None, exempt=None):
+    """critic_q's chain with everything a backward pass needs: x1, as, h1, h2, q (and e_*), mag_q, the pre-activations a1, a2.
+    exempt: this critic's engineered (layer, unit) pairs, left out of `kink`."""
     act = c.get('activation', 'relu')
     a = _f64(a)
     s = _f64(c.get('act_scale'))
@@ -66,13 +74,13 @@ def critic_forward(c, x, a, e_a=None):
     q, e_q, mag = _layer(h2, e_h2, c['W3'], c['b3'])
     kink = np.zeros(x1.shape[0], bool)
     if act == 'relu':
-        kink = (np.abs(a1) <= e_a1).any(1) | (np.abs(a2) <= e_a2).any(1)
+        kink = _kink(a1, e_a1, exempt, 1) | _kink(a2, e_a2, exempt, 2)
     return dict(x1=x1, e_x1=e_x1, as_=as_, e_as=e_as, s=s, a1=a1, e_a1=e_a1, h1=h1, e_h1=e_h1, a2=a2, e_a2=e_a2, h2=h2, e_h2=e_h2,
                 q=q[:, 0], e_q=e_q[:, 0], mag_q=mag[:, 0], kink=kink, act=act)
 
 
-def actor_forward(net, x):
-    """offpolicy_oracle.mlp's chain, per layer."""
+def actor_forward(net, x, exempt=None):
+    """offpolicy_oracle.mlp's chain, per layer.  exempt: this network's engineered (layer, unit) pairs, left out of `kink`."""
     act = net.get('activation', 'relu')
     xn, e_x = _normalise(net, x)
     a1, e_a1, _ = _layer(xn, e_x, net['W1'], net['b1'])
@@ -82,7 +90,7 @@ def actor_forward(net, x):
     m, e_m, mag = _layer(h2, e_h2, net['W3'], net['b3'])
     kink = np.zeros(xn.shape[0], bool)
     if act == 'relu':
-        kink = (np.abs(a1) <= e_a1).any(1) | (np.abs(a2) <= e_a2).any(1)
+        kink = _kink(a1, e_a1, exempt, 1) | _kink(a2, e_a2, exempt, 2)
     return dict(xn=xn, e_xn=e_x, h1=h1, e_h1=e_h1, h2=h2, e_h2=e_h2, m=m, e_m=e_m, mag_m=mag, kink=kink, act=act)
 
 
@@ -97,10 +105,11 @@ def _pack(parts, order, M, stats):
                 stats_bound=np.append((e_st.sum() + gamma(M + 3) * (a_st + e_st).sum()) / M, zeros))
 
 
-def _network_backward(W2, W3, dy, e_dy, S_dy, h1, e_h1, h2, e_h2, act):
-    """delta2, delta1 of a network from dy [M, n_out]: each (value, bound, |.| pass, scale pass)."""
-    ap2, e_ap2 = _act_prime(h2, e_h2, act)
-    ap1, e_ap1 = _act_prime(h1, e_h1, act)
+def _network_backward(W2, W3, dy, e_dy, S_dy, h1, e_h1, h2, e_h2, act, opn=None):
+    """delta2, delta1 of a network from dy [M, n_out]: each (value, bound, |.| pass, scale pass).  opn: the (layer, unit) pairs
+    whose gate reads h >= 0 (wrong='kink_open')."""
+    ap2, e_ap2 = _act_prime(h2, e_h2, act, _units(opn, 2))
+    ap1, e_ap1 = _act_prime(h1, e_h1, act, _units(opn, 1))
     d2, e_d2 = _back(W3, dy, e_dy, ap2, e_ap2, _k(8, 1))
     A_d2 = (np.abs(dy) @ np.abs(W3)) * np.abs(ap2)
     S_d2 = (S_dy @ np.abs(W3)) * np.abs(ap2)
@@ -110,15 +119,16 @@ def _network_backward(W2, W3, dy, e_dy, S_dy, h1, e_h1, h2, e_h2, act):
     return (d2, e_d2, A_d2, S_d2), (d1, e_d1, A_d1, S_d1)
 
 
-def critic_gradient(c, x, a, target, idx=None, wrong=None):
+def critic_gradient(c, x, a, target, idx=None, wrong=None, exempt=None):
     """atacom_offgrad_critic_gradient for one critic on rows x [R, D], a [R, k] (gathered through idx, if given) and target [M]
     (row r of the call) -> dict: flat, bound, scale [64 n1 + 64 + 4096 + 64 + 64 + 1 + 64 k] in the order of PARAMS; stats,
-    stats_bound, stats_scale [4]; kinks; parts.  wrong='no_as_cols': the as columns of a TD3 critic's dW1 zeroed."""
+    stats_bound, stats_scale [4]; kinks; parts.  wrong='no_as_cols': the as columns of a TD3 critic's dW1 zeroed.
+    exempt: this critic's engineered (layer, unit) pairs, left out of `kinks`; wrong='kink_open': their gate reads h >= 0."""
     x, a, t = _f64(x), _f64(a), _f64(target)
     if idx is not None:
         x, a = x[np.asarray(idx)], a[np.asarray(idx)]
     M = x.shape[0]
-    f = critic_forward(c, x, a)
+    f = critic_forward(c, x, a, exempt=exempt)
     act = f['act']
     W2, W3 = _f64(c['W2']), _f64(c['W3'])
     d = f['q'] - t
@@ -126,7 +136,8 @@ def critic_gradient(c, x, a, target, idx=None, wrong=None):
     dy, e_dy = 2.0 * d[:, None], 2.0 * e_d[:, None]
     S_dy = 2.0 * (f['mag_q'] + np.abs(t))[:, None]
     stats = (d * d, (2.0 * np.abs(d) + e_d) * e_d + gamma(2) * d * d, d * d)
-    D2, D1 = _network_backward(W2, W3, dy, e_dy, S_dy, f['h1'], f['e_h1'], f['h2'], f['e_h2'], act)
+    D2, D1 = _network_backward(W2, W3, dy, e_dy, S_dy, f['h1'], f['e_h1'], f['h2'], f['e_h2'], act,
+                               exempt if wrong == 'kink_open' else None)
     DY = (dy, e_dy, np.abs(dy), S_dy)
     one, zero = np.ones((M, 1)), np.zeros((M, 1))
     Mk = _k(M, 3)
@@ -146,18 +157,22 @@ def critic_gradient(c, x, a, target, idx=None, wrong=None):
     return out
 
 
-def actor_gradient(actor, c, x, mean_mode=1, idx=None, action=None, dqda=None, wrong=None):
+def actor_gradient(actor, c, x, mean_mode=1, idx=None, action=None, dqda=None, wrong=None, exempt=None):
     """atacom_offgrad_actor_gradient on rows x [R, D] (gathered through idx, if given) -> dict: flat, bound, scale in the order of
     ACTOR_PARAMS; stats ...; kinks; parts; a, e_a (the action), dqda, e_dqda, scale_dqda [M, k].
     action: the action taken as exact (a device's action_out) instead of the actor's own -- what dqda is then held to;
     dqda: dq/da taken as exact (a device's dqda_out) -- what the actor's gradient is then held to: the critic's part of the
     chain is cut off, and with it its norms.
-    wrong='no_w2a': the W2a branch dropped from dq/da; 'no_scale': the division by the critic's act_scale omitted."""
+    wrong='no_w2a': the W2a branch dropped from dq/da; 'no_scale': the division by the critic's act_scale omitted.
+    exempt: {'actor': pairs, 'critics': [pairs, ...]}, the engineered (layer, unit) pairs of the actor and of the critics (this
+    call reads the first's), left out of `kinks`; wrong='kink_open': their gate reads h >= 0."""
+    ex_a, ex_c = _of(exempt, 'actor'), _of(exempt, 'critics', 0)
+    opn_a, opn_c = (ex_a, ex_c) if wrong == 'kink_open' else (None, None)
     x = _f64(x)
     if idx is not None:
         x = x[np.asarray(idx)]
     M = x.shape[0]
-    fa = actor_forward(actor, x)
+    fa = actor_forward(actor, x, ex_a)
     act = fa['act']
     k = fa['m'].shape[1]
     if mean_mode:
@@ -174,11 +189,11 @@ def actor_gradient(actor, c, x, mean_mode=1, idx=None, action=None, dqda=None, w
         a, e_a = _f64(action), None
     kink = fa['kink'].copy()
     if dqda is None:
-        fc = critic_forward(c, x, a, e_a)
+        fc = critic_forward(c, x, a, e_a, ex_c)
         kink |= fc['kink']
         cact = fc['act']
         W1, W2, W2a, W3 = (_f64(c[n]) for n in ('W1', 'W2', 'W2a', 'W3'))
-        ap2, e_ap2 = _act_prime(fc['h2'], fc['e_h2'], cact)
+        ap2, e_ap2 = _act_prime(fc['h2'], fc['e_h2'], cact, _units(opn_c, 2))
         one, zero = np.ones((M, 1)), np.zeros((M, 1))
         d2, e_d2 = _back(W3, one, zero, ap2, e_ap2, 0)                  # delta2 = W3^T * act'(h2): a product on the vector unit
         A_d2 = np.abs(W3) * np.abs(ap2)
@@ -186,7 +201,7 @@ def actor_gradient(actor, c, x, mean_mode=1, idx=None, action=None, dqda=None, w
         if wrong == 'no_w2a':
             Wb = np.zeros_like(W2a)
         if c['kind'] == TD3:
-            ap1, e_ap1 = _act_prime(fc['h1'], fc['e_h1'], cact)
+            ap1, e_ap1 = _act_prime(fc['h1'], fc['e_h1'], cact, _units(opn_c, 1))
             d1, e_d1 = _back(W2, d2, e_d2, ap1, e_ap1, _k(64, 1))
             A_d1 = (A_d2 @ np.abs(W2)) * np.abs(ap1)
             D = x.shape[1]
@@ -207,7 +222,7 @@ def actor_gradient(actor, c, x, mean_mode=1, idx=None, action=None, dqda=None, w
     e_dm = np.abs(gm) * e_dq + np.abs(dq) * e_gm + e_dq * e_gm + U32 * np.abs(dm)
     S_dm = S_dq * np.abs(gm)
     W2p, W3p = _f64(actor['W2']), _f64(actor['W3'])
-    D2, D1 = _network_backward(W2p, W3p, dm, e_dm, S_dm, fa['h1'], fa['e_h1'], fa['h2'], fa['e_h2'], act)
+    D2, D1 = _network_backward(W2p, W3p, dm, e_dm, S_dm, fa['h1'], fa['e_h1'], fa['h2'], fa['e_h2'], act, opn_a)
     DY = (dm, e_dm, np.abs(dm), S_dm)
     one, zero = np.ones((M, 1)), np.zeros((M, 1))
     Mk = _k(M, 3)
@@ -229,15 +244,16 @@ MEAN_MODES = (1, 0)
 REDRAWS = 200
 
 
-def row_kinks(c):
+def row_kinks(c, exempt=None):
     """Per row of the case's data: a ReLU pre-activation within its forward bound of 0 in a critic at the recorded action, in
     the actor, or in the first critic at the actor's action taken as exact -- there within TWICE the bound, so that the action
-    a device forms, which lies within a small fraction of that bound of the actor's, finds the rows clear as well."""
+    a device forms, which lies within a small fraction of that bound of the actor's, finds the rows clear as well.
+    exempt: {'actor': pairs, 'critics': [pairs, pairs]}, the engineered units left out; every other unit counts as ever."""
     x = c['obs']
-    fa = actor_forward(c['actor'], x)
+    fa = actor_forward(c['actor'], x, _of(exempt, 'actor'))
     bad = fa['kink'].copy()
-    for cr in c['critics']:
-        bad |= critic_forward(cr, x, c['action'])['kink']
+    for j, cr in enumerate(c['critics']):
+        bad |= critic_forward(cr, x, c['action'], exempt=_of(exempt, 'critics', j))['kink']
     if c['mean_mode']:
         sp = _f64(c['actor'].get('act_scale'))
         act = (np.ones(fa['m'].shape[1]) if sp is None else sp) * np.tanh(fa['m'])
@@ -245,7 +261,8 @@ def row_kinks(c):
         act = fa['m']
     f = critic_forward(c['critics'][0], x, act)
     if f['act'] == 'relu':
-        bad |= (np.abs(f['a1']) <= 2.0 * f['e_a1']).any(1) | (np.abs(f['a2']) <= 2.0 * f['e_a2']).any(1)
+        ex = _of(exempt, 'critics', 0)
+        bad |= _kink(f['a1'], f['e_a1'], ex, 1, 2.0) | _kink(f['a2'], f['e_a2'], ex, 2, 2.0)
     return bad
 
 

@@ -104,9 +104,10 @@ def critic_q(c, x, a, e_a=None):
 
 
 def target(actor, critics, next_obs, reward, absorbing, g, eps=None, noise_std=0.0, noise_clip=0.0, low=None, high=None,
-           mean_mode=1, dtype=np.float32):
+           mean_mode=1, dtype=np.float32, wrong=None):
     """-> dict: y, e_y, scale_y [R]; a (= a''), e_a, scale_a [R, k]; q [R, n_critics]; and what the case builder asserts its
-    regimes from: noise_raw (noise_std eps), a_free (a' + n before the action clamp)."""
+    regimes from: noise_raw (noise_std eps), a_free (a' + n before the action clamp).  wrong='absorbing_ge': the flag read as
+    >= 0.5."""
     g, noise_std, noise_clip = (float(dtype(v)) for v in (g, noise_std, noise_clip))
     m, e_m, mag_m = mlp(actor, next_obs)
     if mean_mode:
@@ -127,21 +128,26 @@ def target(actor, critics, next_obs, reward, absorbing, g, eps=None, noise_std=0
     q = np.min([v[0] for v in qs], 0)
     e_q = np.max([v[1] for v in qs], 0)
     mag_q = np.max([v[2] for v in qs], 0)
-    r, keep = _f64(reward), 1.0 - (_f64(absorbing) > 0.5)
+    r, keep = _f64(reward), 1.0 - _absorbed(absorbing, wrong)
     y = r + g * (keep * q)
     e_y = abs(g) * keep * e_q + gamma(2) * (np.abs(r) + np.abs(g * q))
     return dict(y=y, e_y=e_y, scale_y=np.abs(r) + abs(g) * mag_q, a=a2, e_a=e_a, scale_a=scale_a, q=np.stack([v[0] for v in qs], 1),
                 noise_raw=raw, a_free=free)
 
 
-def target_from_action(critics, next_obs, action, reward, absorbing, g, dtype=np.float32):
+def _absorbed(absorbing, wrong=None):
+    assert wrong in (None, 'absorbing_ge')
+    return (_f64(absorbing) >= 0.5) if wrong == 'absorbing_ge' else (_f64(absorbing) > 0.5)
+
+
+def target_from_action(critics, next_obs, action, reward, absorbing, g, dtype=np.float32, wrong=None):
     """The critic half alone, from an action taken as exact (the a'' a device wrote): -> (y, e_y).  The same chain from the
     division on with e_a = 0: the sharper of the two float32 checks, because it does not carry the actor's error through the
     critics' norms."""
     g = float(dtype(g))
     qs = [critic_q(c, next_obs, action) for c in critics]
     q, e_q = np.min([v[0] for v in qs], 0), np.max([v[1] for v in qs], 0)
-    r, keep = _f64(reward), 1.0 - (_f64(absorbing) > 0.5)
+    r, keep = _f64(reward), 1.0 - _absorbed(absorbing, wrong)
     return r + g * (keep * q), abs(g) * keep * e_q + gamma(2) * (np.abs(r) + np.abs(g * q))
 
 

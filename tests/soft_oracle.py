@@ -31,8 +31,8 @@ import math
 import numpy as np
 
 from evaluate_oracle import SAFETY, TANH_ABS, U32, gamma, random_net
-from fit_oracle import _act_prime, _back, _wgrad
-from offgrad_oracle import _k, _network_backward, actor_forward, inside  # noqa: F401
+from fit_oracle import _act_prime, _back, _kink, _units, _wgrad
+from offgrad_oracle import _k, _network_backward, _of, actor_forward, inside  # noqa: F401
 from offpolicy_oracle import _f64, _hidden, _layer, _normalise
 from optim_oracle import EXP_ULPS
 
@@ -89,17 +89,38 @@ def _vec(v, k, default=1.0):
 
 
 # ------------------------------------------------------------------------------------------------------------- forward
-def sample(pol, x, eps, act_scale=None, act_shift=None, wrong=None):
+WRONG_EDGES = ('kink_open', 'tie_second', 'edge_open', 'absorbing_ge')      # each applies to the engineered units, rows, elements only
+
+
+def _cols(exempt, k):
+    """[k] bool: the log sigma elements that a case's description places exactly on a clamp bound."""
+    v = _of(exempt, 'edge')
+    return np.zeros(k, bool) if v is None else np.asarray(v, bool)
+
+
+def _rows(exempt, M):
+    """[M] bool: the rows on which a case's description makes the two critics equal bit for bit."""
+    v = _of(exempt, 'tie')
+    return np.zeros(M, bool) if v is None else np.asarray(v, bool)
+
+
+def sample(pol, x, eps, act_scale=None, act_shift=None, wrong=None, exempt=None):
     """The header's row arithmetic on rows x [M, D] with eps [M, k] -> dict of V: a, logp, t, w, e, p and m, lr; `open` [M, k]
     (the clamp gate), `clamped` [M], `edge` [M] (a log sigma within twice its bound of a clamp bound), `kink` [M], `sat` [M, k]
-    (the float64 allowance 8 * 2^-53 / e).  wrong='no_1e6': the 1e-6 omitted."""
+    (the float64 allowance 8 * 2^-53 / e).  wrong='no_1e6': the 1e-6 omitted.
+    exempt: a case's description (tests/edge_cases.py): {'mu': pairs, 'sigma': pairs} the engineered (layer, unit) pairs left out
+    of `kink`, {'edge': [k] bool} the log sigma elements placed exactly on a bound, left out of `edge`.  wrong='edge_open': the
+    gate of those elements reads lmin <= l_raw <= lmax."""
     eps = _f64(eps)
     k = eps.shape[1]
-    fm, fs = actor_forward(pol['mu'], x), actor_forward(pol['sigma'], x)
+    fm, fs = actor_forward(pol['mu'], x, _of(exempt, 'mu')), actor_forward(pol['sigma'], x, _of(exempt, 'sigma'))
     m, lr = V(fm['m'], fm['e_m'], fm['mag_m']), V(fs['m'], fs['e_m'], fs['mag_m'])
     lmin, lmax = pol['log_std_min'], pol['log_std_max']
     opn = (lmin < lr.v) & (lr.v < lmax)
-    edge = (np.minimum(np.abs(lr.v - lmin), np.abs(lr.v - lmax)) <= 2.0 * lr.e).any(1)
+    cols = _cols(exempt, k)
+    if wrong == 'edge_open':
+        opn = np.where(cols, (lmin <= lr.v) & (lr.v <= lmax), opn)
+    edge = ((np.minimum(np.abs(lr.v - lmin), np.abs(lr.v - lmax)) <= 2.0 * lr.e) & ~cols).any(1)
     lv = np.clip(lr.v, lmin, lmax)
     l = V(lv, np.where(opn, lr.e, 0.0), np.where(opn, lr.s, np.abs(lv)))
     sv = np.exp(l.v)
@@ -129,8 +150,9 @@ def sample(pol, x, eps, act_scale=None, act_shift=None, wrong=None):
                 kink=fm['kink'] | fs['kink'], sat=8.0 * 2.0 ** -53 / np.abs(e.v))
 
 
-def critic_forward(c, x, a, e_a=None):
-    """The plain 2 x 64 critic on [xn | a], a raw, with everything a backward pass needs."""
+def critic_forward(c, x, a, e_a=None, exempt=None):
+    """The plain 2 x 64 critic on [xn | a], a raw, with everything a backward pass needs.  exempt: this critic's engineered
+    (layer, unit) pairs, left out of `kink` and `kink2`."""
     act = c.get('activation', 'relu')
     a = _f64(a)
     xn, e_x = _normalise(c, x)
@@ -144,8 +166,8 @@ def critic_forward(c, x, a, e_a=None):
     kink = np.zeros(x1.shape[0], bool)
     kink2 = kink.copy()
     if act == 'relu':
-        kink = (np.abs(a1) <= e_a1).any(1) | (np.abs(a2) <= e_a2).any(1)
-        kink2 = (np.abs(a1) <= 2.0 * e_a1).any(1) | (np.abs(a2) <= 2.0 * e_a2).any(1)
+        kink = _kink(a1, e_a1, exempt, 1) | _kink(a2, e_a2, exempt, 2)
+        kink2 = _kink(a1, e_a1, exempt, 1, 2.0) | _kink(a2, e_a2, exempt, 2, 2.0)
     return dict(x1=x1, e_x1=e_x1, h1=h1, e_h1=e_h1, h2=h2, e_h2=e_h2, q=V(q[:, 0], e_q[:, 0], mag[:, 0]), kink=kink, kink2=kink2, act=act)
 
 
@@ -155,31 +177,34 @@ def _alpha(log_alpha):
 
 
 def target(pol, critics, next_obs, reward, absorbing, g, log_alpha, eps, act_scale=None, act_shift=None, idx=None, action=None,
-           logp=None, wrong=None):
+           logp=None, wrong=None, exempt=None):
     """atacom_soft_target -> dict: y (V), a, logp (V), q [2] (V), tie [M], kink [M], edge [M], sat [M] (the float64 allowance on y).
     action, logp: a device's action_out and logp_out taken as exact -- what y is then held to (offpolicy_oracle's
     target_from_action): the bound of the whole chain covers no row whose critic has a ReLU pre-activation within the error that
     the action's own bound gives it (`kinks_e2e` counts them: zero for tanh networks, most rows for ReLU).
     `kink`, `tie`: at the action taken as exact, within TWICE the bounds.
-    wrong='larger': the larger critic; 'absorbing': (1 - absorbing) applied to q but not to alpha logp; 'no_1e6'."""
+    wrong='larger': the larger critic; 'absorbing': (1 - absorbing) applied to q but not to alpha logp; 'no_1e6'.
+    exempt: a case's description (sample's keys, and {'critics': [pairs, pairs]} for the pair this call is given, {'tie': [M]
+    bool} the rows of an engineered tie): left out of kink, edge and tie; nothing else is.  wrong='absorbing_ge': the flag read
+    as >= 0.5; 'edge_open' (sample)."""
     x, r, ab = _f64(next_obs), _f64(reward), _f64(absorbing)
     if idx is not None:
         x, r, ab = x[np.asarray(idx)], r[np.asarray(idx)], ab[np.asarray(idx)]
-    s = sample(pol, x, eps, act_scale, act_shift, wrong=wrong)
+    s = sample(pol, x, eps, act_scale, act_shift, wrong=wrong, exempt=exempt)
     cut = action is not None
     a_v = _f64(action) if cut else s['a'].v
-    fq = [critic_forward(c, x, a_v, None if cut else s['a'].e) for c in critics]
-    fx = fq if cut else [critic_forward(c, x, a_v) for c in critics]
+    fq = [critic_forward(c, x, a_v, None if cut else s['a'].e, _of(exempt, 'critics', j)) for j, c in enumerate(critics)]
+    fx = fq if cut else [critic_forward(c, x, a_v, exempt=_of(exempt, 'critics', j)) for j, c in enumerate(critics)]
     q1, q2 = fq[0]['q'], fq[1]['q']
     two = q2.v < q1.v
     if wrong == 'larger':
         two = ~two
     q = V(np.where(two, q2.v, q1.v), np.where(two, q2.e, q1.e), np.where(two, q2.s, q1.s))
-    tie = np.abs(fx[0]['q'].v - fx[1]['q'].v) <= 2.0 * (fx[0]['q'].e + fx[1]['q'].e)
+    tie = (np.abs(fx[0]['q'].v - fx[1]['q'].v) <= 2.0 * (fx[0]['q'].e + fx[1]['q'].e)) & ~_rows(exempt, x.shape[0])
     al = _alpha(log_alpha)
     lp = s['logp'] if logp is None else V(_f64(logp))
     z1 = mul(al, lp)
-    keep = V(np.where(ab > 0.5, 0.0, 1.0))
+    keep = V(np.where((ab >= 0.5) if wrong == 'absorbing_ge' else (ab > 0.5), 0.0, 1.0))
     if wrong == 'absorbing':
         z = add(mul(keep, q), z1, -1.0)
     else:
@@ -191,9 +216,11 @@ def target(pol, critics, next_obs, reward, absorbing, g, log_alpha, eps, act_sca
 
 
 # ------------------------------------------------------------------------------------------------------------ backward
-def _grads(net, fwd, dy, x_in, e_x_in, M):
-    """{name: (value, bound, scale)} of a network's six tensors from dy (a V [M, n_out]), unscaled by 1 / M."""
-    D2, D1 = _network_backward(_f64(net['W2']), _f64(net['W3']), dy.v, dy.e, dy.s, fwd['h1'], fwd['e_h1'], fwd['h2'], fwd['e_h2'], fwd['act'])
+def _grads(net, fwd, dy, x_in, e_x_in, M, opn=None):
+    """{name: (value, bound, scale)} of a network's six tensors from dy (a V [M, n_out]), unscaled by 1 / M.  opn: the (layer,
+    unit) pairs whose gate reads h >= 0 (wrong='kink_open')."""
+    D2, D1 = _network_backward(_f64(net['W2']), _f64(net['W3']), dy.v, dy.e, dy.s, fwd['h1'], fwd['e_h1'], fwd['h2'], fwd['e_h2'], fwd['act'],
+                               opn)
     DY = (dy.v, dy.e, np.abs(dy.v), dy.s)
     one, zero = np.ones((M, 1)), np.zeros((M, 1))
     Mk = _k(M, 3)
@@ -217,27 +244,29 @@ def _pack(parts, M, stats):
     return dict(flat=flat(0), bound=flat(1), scale=flat(2), parts=parts, stats=st[0], stats_bound=st[1], stats_scale=st[2])
 
 
-def critic_gradient(c, x, a, tgt, idx=None):
-    """atacom_soft_critic_gradient for one critic -> dict: flat, bound, scale in the order of PARAMS; stats...; kinks."""
+def critic_gradient(c, x, a, tgt, idx=None, exempt=None, wrong=None):
+    """atacom_soft_critic_gradient for one critic -> dict: flat, bound, scale in the order of PARAMS; stats...; kinks.
+    exempt: this critic's engineered (layer, unit) pairs, left out of `kinks`; wrong='kink_open': their gate reads h >= 0."""
+    assert wrong in (None, 'kink_open')
     x, a, t = _f64(x), _f64(a), _f64(tgt)
     if idx is not None:
         x, a = x[np.asarray(idx)], a[np.asarray(idx)]
     M = x.shape[0]
-    f = critic_forward(c, x, a)
+    f = critic_forward(c, x, a, exempt=exempt)
     d = add(f['q'], V(t), -1.0)
     d = V(d.v, d.e, f['q'].s + np.abs(t))
     dy = V(2.0 * d.v[:, None], 2.0 * d.e[:, None], 2.0 * d.s[:, None])
-    out = _pack(_grads(c, f, dy, f['x1'], f['e_x1'], M), M, [mul(d, d)])
+    out = _pack(_grads(c, f, dy, f['x1'], f['e_x1'], M, exempt if wrong == 'kink_open' else None), M, [mul(d, d)])
     out['kinks'] = int(f['kink'].sum())
     return out
 
 
-def dqda(c, f, D):
-    """dq/da of a critic from its forward dict: the a-columns of W1^T delta1 -> V [M, k]."""
+def dqda(c, f, D, opn=None):
+    """dq/da of a critic from its forward dict: the a-columns of W1^T delta1 -> V [M, k].  opn: as in _grads."""
     W1, W2, W3 = (_f64(c[n]) for n in ('W1', 'W2', 'W3'))
     M = f['h1'].shape[0]
-    ap2, e_ap2 = _act_prime(f['h2'], f['e_h2'], f['act'])
-    ap1, e_ap1 = _act_prime(f['h1'], f['e_h1'], f['act'])
+    ap2, e_ap2 = _act_prime(f['h2'], f['e_h2'], f['act'], _units(opn, 2))
+    ap1, e_ap1 = _act_prime(f['h1'], f['e_h1'], f['act'], _units(opn, 1))
     d2, e_d2 = _back(W3, np.ones((M, 1)), np.zeros((M, 1)), ap2, e_ap2, 0)
     A_d2 = np.abs(W3) * np.abs(ap2)
     d1, e_d1 = _back(W2, d2, e_d2, ap1, e_ap1, _k(64, 1))
@@ -249,7 +278,7 @@ def dqda(c, f, D):
 
 
 def actor_gradient(pol, critics, x, eps, log_alpha, target_entropy, act_scale=None, act_shift=None, idx=None, action=None, q=None,
-                   dq=None, wrong=None):
+                   dq=None, wrong=None, exempt=None):
     """atacom_soft_actor_gradient -> dict: mu, sigma (each flat, bound, scale, parts), stats, stats_bound, stats_scale [4]
     (from mu's pack), a, logp (V), q (V, V), dqda (V), two [M], flags kink / tie / edge [M].
     The chain can be cut at a device's own intermediates, as offgrad_oracle.actor_gradient's:
@@ -257,27 +286,31 @@ def actor_gradient(pol, critics, x, eps, log_alpha, target_entropy, act_scale=No
       q [M, 2]: the critics' values taken as exact (q_out): they decide the selection;
       dq [M, k]: dq/da taken as exact (dqda_out) -- what the gradients are then held to.
     wrong='no_alpha': the -alpha term of dl dropped; 'no_gate': the clamp gate ignored; 'larger': the larger critic selected;
-    'no_1e6'; 'no_scale': act_scale missing from du."""
+    'no_1e6'; 'no_scale': act_scale missing from du.
+    exempt: a case's description (target's keys): what it engineers is left out of kink, tie and edge; nothing else is.  On the
+    engineered units, rows and elements only: wrong='kink_open': the ReLU gate reads h >= 0; 'tie_second': q_2 <= q_1 selects
+    critic 2; 'edge_open': the clamp gate reads lmin <= l_raw <= lmax."""
     x = _f64(x)
     if idx is not None:
         x = x[np.asarray(idx)]
     M, D = x.shape
-    s = sample(pol, x, eps, act_scale, act_shift, wrong=wrong)
+    opn = (exempt or {}) if wrong == 'kink_open' else {}
+    s = sample(pol, x, eps, act_scale, act_shift, wrong=wrong, exempt=exempt)
     k = s['a'].v.shape[1]
     a_v, a_e = (s['a'].v, s['a'].e) if action is None else (_f64(action), None)
-    fq = [critic_forward(c, x, a_v, a_e) for c in critics]
-    fx = fq if a_e is None else [critic_forward(c, x, a_v) for c in critics]
+    fq = [critic_forward(c, x, a_v, a_e, _of(exempt, 'critics', j)) for j, c in enumerate(critics)]
+    fx = fq if a_e is None else [critic_forward(c, x, a_v, exempt=_of(exempt, 'critics', j)) for j, c in enumerate(critics)]
     q1, q2 = fq[0]['q'], fq[1]['q']
-    tie = np.abs(fx[0]['q'].v - fx[1]['q'].v) <= 2.0 * (fx[0]['q'].e + fx[1]['q'].e)
-    if q is not None:
-        q = _f64(q)
-        two = q[:, 1] < q[:, 0]
-    else:
-        two = q2.v < q1.v
+    tied = _rows(exempt, M)
+    tie = (np.abs(fx[0]['q'].v - fx[1]['q'].v) <= 2.0 * (fx[0]['q'].e + fx[1]['q'].e)) & ~tied
+    qa, qb = (q1.v, q2.v) if q is None else (_f64(q)[:, 0], _f64(q)[:, 1])
+    two = qb < qa
     if wrong == 'larger':
         two = ~two
+    if wrong == 'tie_second':
+        two = np.where(tied, qb <= qa, two)
     qs = V(np.where(two, q2.v, q1.v), np.where(two, q2.e, q1.e), np.where(two, q2.s, q1.s))
-    g1, g2 = dqda(critics[0], fq[0], D), dqda(critics[1], fq[1], D)
+    g1, g2 = dqda(critics[0], fq[0], D, _of(opn, 'critics', 0)), dqda(critics[1], fq[1], D, _of(opn, 'critics', 1))
     sel = two[:, None]
     gq = V(np.where(sel, g2.v, g1.v), np.where(sel, g2.e, g1.e), np.where(sel, g2.s, g1.s))
     dqv = gq if dq is None else V(_f64(dq))
@@ -294,8 +327,8 @@ def actor_gradient(pol, critics, x, eps, log_alpha, target_entropy, act_scale=No
     term = add(mul(al, s['logp']), qs, -1.0)
     ent = add(s['logp'], V(np.float64(target_entropy)))
     stats = [term, s['logp'], V(-ent.v, ent.e, ent.s), V(s['clamped'].astype(np.float64))]
-    out = dict(mu=_pack(_grads(pol['mu'], fm, dm, fm['xn'], fm['e_xn'], M), M, stats),
-               sigma=_pack(_grads(pol['sigma'], fs, dl, fs['xn'], fs['e_xn'], M), M, []))
+    out = dict(mu=_pack(_grads(pol['mu'], fm, dm, fm['xn'], fm['e_xn'], M, _of(opn, 'mu')), M, stats),
+               sigma=_pack(_grads(pol['sigma'], fs, dl, fs['xn'], fs['e_xn'], M, _of(opn, 'sigma')), M, []))
     out.update(stats=out['mu']['stats'], stats_bound=out['mu']['stats_bound'], stats_scale=out['mu']['stats_scale'], a=s['a'],
                logp=s['logp'], q=(q1, q2), dqda=gq, two=two, tie=tie, edge=s['edge'], clamped=s['clamped'], open=s['open'], lr=s['lr'],
                kink=s['kink'] | fx[0]['kink2'] | fx[1]['kink2'], kinks_e2e=int((fq[0]['kink'] | fq[1]['kink']).sum()), sat=s['sat'],
@@ -346,15 +379,16 @@ def random_soft_critic(rng, D, k, activation, normalise, dtype):
     return c
 
 
-def row_flags(c):
+def row_flags(c, exempt=None):
     """Per row of the case's data: at a ReLU kink (of a policy network, of a critic at the recorded action, of a critic at the
-    policy's action within TWICE its bound), at a tie of the two critics, or at a clamp edge -- for the online and the target pair."""
+    policy's action within TWICE its bound), at a tie of the two critics, or at a clamp edge -- for the online and the target pair.
+    exempt: a case's description (target's keys; 'critics' describes both pairs): what it engineers is left out, nothing else."""
     x, sc, sh = c['obs'], c['act_scale'], c['act_shift']
     bad = np.zeros(x.shape[0], bool)
-    for cr in c['critics']:
-        bad |= critic_forward(cr, x, c['action'])['kink']
+    for j, cr in enumerate(c['critics']):
+        bad |= critic_forward(cr, x, c['action'], exempt=_of(exempt, 'critics', j))['kink']
     for pair in (c['critics'], c['targets']):
-        t = target(c['policy'], pair, x, c['reward'], c['absorbing'], c['gamma'], c['log_alpha'], c['eps'], sc, sh)
+        t = target(c['policy'], pair, x, c['reward'], c['absorbing'], c['gamma'], c['log_alpha'], c['eps'], sc, sh, exempt=exempt)
         bad |= t['kink'] | t['tie'] | t['edge']
         if not c['saturate']:
             bad |= (np.abs(t['u'].v) + t['u'].e > U_MAX).any(1)

@@ -35,7 +35,7 @@ import numpy as np
 
 import evaluate_oracle as eo
 import fit_oracle as fo
-from fit_oracle import SAFETY, U32, _act_prime, _back, _wgrad, forward, gamma
+from fit_oracle import SAFETY, U32, _act_prime, _back, _kink, _units, _wgrad, forward, gamma
 
 NAMES = fo.NAMES + ('log_std',)
 
@@ -85,12 +85,14 @@ def _times(p, e_p, ap, e_ap):
 MISTAKES = ('V2 transposed', "act'(a2) dropped from the tangent", 'std in place of std^2')
 
 
-def fvp(net, std, x, v, damping=0.0, idx=None, mistake=None):
+def fvp(net, std, x, v, damping=0.0, idx=None, mistake=None, exempt=None):
     """The call of atacom_trust_fvp on rows x [R, n_in] (gathered through idx, if given), direction v [P + n_out] -> dict:
     flat, bound, scale [P + n_out] in the library's order (bound: float32, per element; scale: the pass on absolute values);
     kinks: the number of rows the bound does not cover (module docstring).  `mistake`: one of MISTAKES, made on purpose -- what
-    a wrong device would return, for the tests that show that the bound and the norm rule catch it."""
-    assert mistake is None or mistake in MISTAKES
+    a wrong device would return, for the tests that show that the bound and the norm rule catch it.
+    exempt: the engineered (layer, unit) pairs of tests/edge_cases.py, left out of `kinks`; nothing else is.
+    mistake='kink_open': the gate of those units reads h >= 0, in the tangent and in the backward pass."""
+    assert mistake is None or mistake in MISTAKES or mistake == 'kink_open'
     x, s, v = _f64(x), _f64(std), _f64(v)
     act = net.get('activation', 'relu')
     if idx is not None:
@@ -104,9 +106,10 @@ def fvp(net, std, x, v, damping=0.0, idx=None, mistake=None):
     f = forward(net, x)
     kink = np.zeros(M, bool)
     if act == 'relu':
-        kink |= (np.abs(f['a1']) <= SAFETY * f['e_a1']).any(1) | (np.abs(f['a2']) <= SAFETY * f['e_a2']).any(1)
-    ap1, e_ap1 = _act_prime(f['h1'], f['e_h1'], act)
-    ap2, e_ap2 = _act_prime(f['h2'], f['e_h2'], act)
+        kink |= _kink(f['a1'], f['e_a1'], exempt, 1, SAFETY) | _kink(f['a2'], f['e_a2'], exempt, 2, SAFETY)
+    opn = exempt if mistake == 'kink_open' else None
+    ap1, e_ap1 = _act_prime(f['h1'], f['e_h1'], act, _units(opn, 1))
+    ap2, e_ap2 = _act_prime(f['h2'], f['e_h2'], act, _units(opn, 2))
     tp2 = np.ones_like(ap2) if mistake == MISTAKES[1] else ap2
     # ---- tangent
     n1 = 4 * ((n_in + 3) // 4)
@@ -212,23 +215,28 @@ def direction(rng, net, n_out, dtype):
     return join(parts).astype(dtype)
 
 
-def case(seed, n_in, n_out, activation, normalise, rows, dtype=np.float32, check=True):
+def case(seed, n_in, n_out, activation, normalise, rows, dtype=np.float32, check=True, edge=None, damping=DAMPING):
     """A case in `dtype`: dict(net, x, std, v, g, damping, want).  net, x and std are evaluate_oracle.case_data's (std
     log-uniform in [1e-2, 2]); v and g are two directions.  The seed is moved on, deterministically, until no row sits at a relu
-    kink: zero exclusions, asserted."""
+    kink: zero exclusions, asserted.  edge: a construction of tests/edge_cases.py, edge(net, x) -> the engineered (layer, unit)
+    pairs; it changes net and x in place, the directions are drawn before it from the network as drawn (so that they are not
+    zero on the engineered rows), and its units alone are left out of the count (c['exempt'])."""
+    exempt = None
     for attempt in range(64):
         s = seed + 1000 * attempt
         net, x, _, std = eo.case_data(s, n_in, n_out, activation, normalise, rows, dtype)
         rng = np.random.default_rng(s + 99)
         v, g = direction(rng, net, n_out, dtype), direction(rng, net, n_out, dtype)
-        want = fvp(net, std, x, v, DAMPING)
+        if edge is not None:
+            exempt = edge(net, x)
+        want = fvp(net, std, x, v, damping, exempt=exempt)
         if want['kinks'] == 0:
             break
     if check:
         assert want['kinks'] == 0, 'no seed without a row at a kink'
     # the right-hand side of the conjugate-gradient tests: (F + damping I) g, a vector the first iterations make progress on
-    rhs = fvp(net, std, x, g, DAMPING)['flat'].astype(dtype)
-    return dict(net=net, x=x, std=std, v=v, g=g, rhs=rhs, damping=DAMPING, want=want, n_in=n_in, n_out=n_out)
+    rhs = fvp(net, std, x, g, damping)['flat'].astype(dtype)
+    return dict(net=net, x=x, std=std, v=v, g=g, rhs=rhs, damping=damping, want=want, n_in=n_in, n_out=n_out, exempt=exempt)
 
 
 # ---- the TRPO policy step
