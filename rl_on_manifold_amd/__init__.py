@@ -44,6 +44,9 @@ def __getattr__(name):
     if name in ('critic_gradient', 'actor_gradient', 'QGradients'):
         from . import offgrad
         return getattr(offgrad, name)
+    if name in ('TrackedAdam', 'GraphedFit'):
+        from . import offstep
+        return getattr(offstep, name)
     if name in ('SoftCritic', 'soft_td_target', 'soft_critic_gradient', 'soft_actor_gradient', 'AlphaAdam', 'ActorGradients'):
         from . import soft
         return getattr(soft, name)

@@ -21,7 +21,9 @@ include/atacom_optim_hip.h), the ninth library, and libatacom_trust.so (the Fish
 include/atacom_trust_hip.h), the tenth, and libatacom_offpolicy.so (the critic's Q-value, the fused TD target and the soft target
 update of DDPG and TD3, include/atacom_offpolicy_hip.h), the eleventh, and libatacom_offgrad.so (the critic and actor gradients of a
 DDPG / TD3 update, include/atacom_offgrad_hip.h), the twelfth, and libatacom_soft.so (the soft TD target, the critic and actor
-gradients and the temperature step of a SAC update, include/atacom_soft_hip.h), the thirteenth; build_additions() builds its rows.
+gradients and the temperature step of a SAC update, include/atacom_soft_hip.h), the thirteenth, and libatacom_offstep.so (the Adam
+step of an off-policy update with the soft update of the target networks in the same launch, include/atacom_offstep_hip.h), the
+fourteenth; build_additions() builds its rows.
 csrc/mlp/ is no library and has no row in any table: it holds the headers that libatacom_fit.so, libatacom_trust.so,
 libatacom_offgrad.so and libatacom_soft.so share (the backward pass of the 2 x 64 network, atacom_mlp_backward.h; the host checks
 of a call's views, atacom_view_checks.h, which libatacom_offpolicy.so includes too), which sources() finds through their #include
@@ -57,13 +59,15 @@ UNITS = ['atacom_iiwa.hip', 'atacom_iiwa_group.hip', 'atacom_iiwa_f64.hip', 'ata
 # adds none.  atacom_optim.hip: every operation of the Adam step is the individually rounded one its header writes; so are the
 # target arithmetic and the soft update of atacom_offpolicy.hip (the fused multiply-adds of its float64 networks are explicit) and
 # the row arithmetic of atacom_offgrad.hip (squash, its derivative, the division by act_scale, the head) and of atacom_soft.hip
-# (the squashed Gaussian's sample, its log-probability and their derivatives, the target, the temperature's Adam step)
+# (the squashed Gaussian's sample, its log-probability and their derivatives, the target, the temperature's Adam step) and the
+# Adam step and target update of atacom_offstep.hip, whose bits are those of atacom_optim.hip and of the soft update
 UNIT_FLAGS = {'atacom_iiwa_group.hip': ['-mllvm', '-amdgpu-sched-strategy=iterative-ilp'],
               'atacom_returns.hip': ['-ffp-contract=off'],
               'atacom_optim.hip': ['-ffp-contract=off'],
               'atacom_offpolicy.hip': ['-ffp-contract=off'],
               'atacom_offgrad.hip': ['-ffp-contract=off'],
-              'atacom_soft.hip': ['-ffp-contract=off']}
+              'atacom_soft.hip': ['-ffp-contract=off'],
+              'atacom_offstep.hip': ['-ffp-contract=off']}
 
 # One row per library, keyed by its name: the units it compiles and `tuning`, whether it takes the ATACOM_ONLY_UNITS /
 # kept-object path below.  Everything else follows from the key (_binding.naming()).  A new library is a new row here, a
@@ -115,6 +119,7 @@ ADDITIONS = {
     'offpolicy': _target('offpolicy', ['atacom_offpolicy.hip', 'atacom_offpolicy_capi.cpp'], False, sub='offpolicy'),
     'offgrad': _target('offgrad', ['atacom_offgrad.hip', 'atacom_offgrad_capi.cpp'], False, sub='offgrad'),
     'soft': _target('soft', ['atacom_soft.hip', 'atacom_soft_capi.cpp'], False, sub='soft'),
+    'offstep': _target('offstep', ['atacom_offstep.hip', 'atacom_offstep_capi.cpp'], False, sub='offstep'),
 }
 """The open table: rows of the same kind as TARGETS and EXTENSIONS, and rows MAY BE APPENDED.  TARGETS and EXTENSIONS are
 pinned entry by entry by the tests that guard them; this one is checked row by row (each row's own properties, and that the
@@ -131,7 +136,10 @@ backward pass of csrc/mlp/, which it shares with 'fit', 'trust' and 'soft', and 
 directories of 'fit', 'trust', 'optim' or 'offpolicy'.
 'soft': a SAC update (include/atacom_soft_hip.h): the fused soft target, the critics' and the squashed-Gaussian actor's gradients
 and Adam on log_alpha; it borrows what 'offgrad' borrows, csrc/mlp/ included, and declares its own critic descriptor: nothing of
-the directories of 'fit', 'trust', 'optim', 'offpolicy' or 'offgrad'."""
+the directories of 'fit', 'trust', 'optim', 'offpolicy' or 'offgrad'.
+'offstep': the Adam step of an off-policy update with the target networks' soft update in its launch
+(include/atacom_offstep_hip.h); it borrows the host scaffolding by `#include "../..."` as 'optim' does, nothing of csrc/mlp/ and
+nothing of another library's directory, and lends nothing."""
 
 
 def _row(name):
