@@ -1,9 +1,10 @@
 // Launchers of libatacom_offgrad.so (include/atacom_offgrad_hip.h): what the C-ABI file calls after it has validated a call,
 // and the sizes both sides agree on.  The kernels are in atacom_offgrad.hip; nothing here touches the device.  The workgroup and
-// tile constants, tiles() and effective_blocks() are those of ../mlp/atacom_mlp_backward.h.
+// tile constants, tiles() and effective_blocks() are those of ../mlp/atacom_mlp_backward.h, RowView is that of
+// ../mlp/atacom_mlp_forward.h.
 #pragma once
 #include "../../../include/atacom_offgrad_hip.h"
-#include "../mlp/atacom_mlp_backward.h"
+#include "../mlp/atacom_mlp_forward.h"
 
 namespace atacom_offgrad {
 
@@ -21,11 +22,6 @@ __host__ __device__ inline int64_t partial_size(int n_in, int n_out, int n_act) 
 struct NetDesc {
     const void *W1, *b1, *W2, *b2, *W2a, *W3, *b3, *shift, *scale, *act_scale;
     int n1, n_out, activation, mean_mode;
-};
-
-struct RowView {
-    const void* ptr;
-    int64_t so, si;
 };
 
 // A validated critic call: n_nets critics on the same rows.

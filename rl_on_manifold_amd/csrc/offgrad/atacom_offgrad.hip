@@ -7,10 +7,14 @@
 // mlp_forward_mfma, mlp_act16, mlp_act, wave_lds_fence and num<T>.  From ../mlp/atacom_mlp_backward.h (namespace
 // atacom_mlp_backward, shared with the fit, trust and soft units), which states the float32 mappings: the row access,
 // the transposition buffers, the backward pass from dy on, the accumulators with their hand-over and store, the float64
-// backward loops, column pairs and accumulation, the slice sum of the reduction and the CH switch.  Layer 2 of the critic has
-// two branches, so its gradient takes the header's WA flag (dW2a = sum delta2 as^T rides on dW2's A operands).  This unit's own:
-// TD3's first-layer input [xn | as], and the critic's INPUT gradient, W2a^T delta2 (+ W1[:, D:]^T delta1), which the actor call
-// needs and no weight-gradient pass produces; it comes out like the deltas, element 4 g + v of row n16 in register v.
+// backward loops, column pairs and accumulation, the slice sum of the reduction and the CH switch.  From
+// ../mlp/atacom_mlp_forward.h (the same namespace, shared with the soft unit): the block's layout LdsM with W2A and AUX, the
+// staging of a network's weights (stage_weights), obs_elem, the float64 layers (normalise_f64, hidden_f64, head_f64),
+// pick_fields and the launchers' RowView / rows_of.  Layer 2 of the critic has two branches, so staging and gradient take the
+// headers' WA flag (dW2a = sum delta2 as^T rides on dW2's A operands).  This unit's own: its Net and the AUX words,
+// forward_block, the scaled action as and TD3's first-layer input [xn | as], and the critic's INPUT gradient, W2a^T delta2
+// (+ W1[:, D:]^T delta1), which the actor call needs and no weight-gradient pass produces; it comes out like the deltas,
+// element 4 g + v of row n16 in register v.
 // LDS: one network block MlpLdsM<4 CH, 64, 8>::NET with W2a [64][8] in rows 8 .. 15 of its W3 block (whose outputs are never
 // stored), 8 floats, and 8 KB of staging per wavefront: 63808 bytes.  The kernels are bound to one wavefront per SIMD.
 //
@@ -57,54 +61,22 @@ struct ActorParams {
 };
 
 // ------------------------------------------------------------------------------------------------------------ float32
-template <int CH>
-struct LdsM : atacom::MlpLdsM<4 * CH, H, NK> {
-    using L = atacom::MlpLdsM<4 * CH, H, NK>;
-    static constexpr int W2A = L::W3 + 8 * L::S2;      // [64][8]
-    static constexpr int AUX = L::EXPLORE;             // act_scale [8]
-    static_assert(H * 8 <= 8 * L::S2, "W2a fits the unread half of the W3 block");
-};
+// AUX of the block: act_scale [8]
+template <typename T>
+__device__ __forceinline__ void pick_net(Net<T>& n, bool second, const Net<T>& a, const Net<T>& b) {
+    using N = Net<T>;
+    pick_fields(n, second, a, b, &N::W1, &N::b1, &N::W2, &N::b2, &N::W2a, &N::W3, &N::b3, &N::shift, &N::scale, &N::act_scale, &N::n1,
+                &N::n_out, &N::activation, &N::mean_mode);
+}
 
-// Every word a phase reads is written here, the padding as zero: the W1 slots at or past n1 (the actor's n_in = D <= 4 CH), the
-// W3 rows and biases from n_out to 7, the W2a columns at or past n_act (all of them for the actor).
+// the header's stage_weights (W2a: all zero for the actor) and this unit's AUX words, between the two barriers of a phase
 template <int CH>
 __device__ __forceinline__ void stage_net(const Net<float>& n, int n_obs, int n_act, float* lds, int tid) {
     using L = LdsM<CH>;
     __syncthreads();                                   // the phase before has read its weights
-    // The actor kernel stages inside its loop over the rounds.  Left visible, the per-thread source addresses of every staging
-    // iteration (they divide by n1) are hoisted out of that loop as 64-bit pairs and spill to scratch; an opaque thread index
-    // keeps them where they are used.
-    asm volatile("" : "+v"(tid));
-    for (int i = tid; i < H * L::S1; i += kBlock) {      // [unit][g][8], slot s of group g = element CH g + s
-        const int u = i / L::S1, g = (i % L::S1) / 8, s = i % 8, e = CH * g + s;
-        lds[L::W1 + i] = (s < CH && e < n.n1) ? n.W1[u * n.n1 + e] : 0.0f;
-    }
-    for (int i = tid; i < H * H; i += kBlock) lds[L::W2 + (i / H) * L::S2 + (i % H)] = n.W2[i];
-    for (int i = tid; i < 8 * H; i += kBlock) lds[L::W3 + (i / H) * L::S2 + (i % H)] = i < n.n_out * H ? n.W3[i] : 0.0f;
-    for (int i = tid; i < 8 * L::S2; i += kBlock) {      // rows 8 .. 15 of the W3 block: W2a [64][8], then zeros
-        const int u = i / 8, k = i % 8;
-        lds[L::W2A + i] = (n.W2a && u < H && k < n_act) ? n.W2a[u * n_act + k] : 0.0f;
-    }
-    for (int i = tid; i < H; i += kBlock) { lds[L::B1 + i] = n.b1[i]; lds[L::B2 + i] = n.b2[i]; }
-    for (int i = tid; i < 16; i += kBlock) lds[L::B3 + i] = i < n.n_out ? n.b3[i] : 0.0f;
-    for (int i = tid; i < 32; i += kBlock) {             // [g][8] like W1; past the observation: shift 0, scale 1
-        const int g = i / 8, s = i % 8, e = CH * g + s;
-        const bool real = s < CH && e < n_obs;
-        lds[L::SHIFT + i] = (real && n.shift) ? n.shift[e] : 0.0f;
-        lds[L::SCALE + i] = (real && n.scale) ? n.scale[e] : 1.0f;
-    }
+    stage_weights<CH, true>(n, n_obs, n_act, lds, tid);
     for (int i = tid; i < 8; i += kBlock) lds[L::AUX + i] = (i < n_act && n.act_scale) ? n.act_scale[i] : 1.0f;
     __syncthreads();
-}
-
-// element e of the normalised observation of the row at xr; 0 at or past n_obs.  The load is under the full exec mask.
-template <int CH>
-__device__ __forceinline__ float obs_elem(const float* lds, const float* xr, int e, int n_obs) {
-    using L = LdsM<CH>;
-    const int ec = e < n_obs ? e : n_obs - 1;
-    const int slot = 8 * (ec / CH) + ec % CH;
-    const float v = (xr[ec] - lds[L::SHIFT + slot]) * lds[L::SCALE + slot];
-    return e < n_obs ? v : 0.0f;
 }
 
 // element k of as = a / act_scale of the row at ar; 0 outside 0 .. n_act - 1
@@ -191,14 +163,8 @@ __device__ __forceinline__ void critic_f32(const CriticParams<float>& p) {
     constexpr int kLds = L::NET + kExtra + kWaves * kStage;
     __shared__ __attribute__((aligned(16))) float lds[kLds];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n16 = lane & 15, g = lane >> 4;
-    // (selected field by field, not indexed: a run-time index into the kernel's argument block would put it in scratch)
     Net<float> net;
-    const bool second = blockIdx.y != 0;
-#define OFFGRAD_PICK(f) net.f = second ? p.net[1].f : p.net[0].f
-    OFFGRAD_PICK(W1); OFFGRAD_PICK(b1); OFFGRAD_PICK(W2); OFFGRAD_PICK(b2); OFFGRAD_PICK(W2a); OFFGRAD_PICK(W3); OFFGRAD_PICK(b3);
-    OFFGRAD_PICK(shift); OFFGRAD_PICK(scale); OFFGRAD_PICK(act_scale); OFFGRAD_PICK(n1); OFFGRAD_PICK(n_out);
-    OFFGRAD_PICK(activation); OFFGRAD_PICK(mean_mode);
-#undef OFFGRAD_PICK
+    pick_net(net, blockIdx.y != 0, p.net[0], p.net[1]);
     stage_net<CH>(net, p.n_obs, p.n_act, lds, threadIdx.x);
     float* t_act = lds + L::NET + kExtra + wave * kStage;      // activations [16][64]
     float* t_del = t_act + 1024;                                // deltas [16][64]; before them: q [16][8], dy [16][8]
@@ -493,38 +459,13 @@ __device__ __forceinline__ void entry_columns(int e, int n_in, int n_act, const 
 
 constexpr int kMaxQ = H * 32 + H + H * H + H + H * NK + NK + H * NK + kStats, kNQ = (kMaxQ + kBlock - 1) / kBlock;
 
-// two hidden layers of a network from the columns cx (n_in values) and, with W2a, AS, into the columns ch1, ch2
-__device__ __forceinline__ void hidden_f64(const Net<double>& n, double* me, int cx, int ch1, int ch2, int n_act, bool live, int c) {
-    if (live)
-        for (int j = c; j < H; j += 16) {
-            double a = n.b1[j];
-            for (int e = 0; e < n.n1; ++e) a = __builtin_fma(n.W1[j * n.n1 + e], me[cx + e], a);
-            me[ch1 + j] = atacom::mlp_act(a, n.activation);
-        }
-    __syncthreads();
-    if (live)
-        for (int j = c; j < H; j += 16) {
-            double a = n.b2[j];
-            for (int i = 0; i < H; ++i) a = __builtin_fma(n.W2[j * H + i], me[ch1 + i], a);
-            if (n.W2a)
-                for (int k = 0; k < n_act; ++k) a = __builtin_fma(n.W2a[j * n_act + k], me[Rec::AS + k], a);
-            me[ch2 + j] = atacom::mlp_act(a, n.activation);
-        }
-    __syncthreads();
-}
-
 __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
     constexpr int R = kRowsF64;
     using C = Rec;
     __shared__ double rec[R * C::SIZE];
     const int tid = threadIdx.x, row = tid >> 4, c = tid & 15;
     Net<double> net;
-    const bool second = blockIdx.y != 0;
-#define OFFGRAD_PICK(f) net.f = second ? p.net[1].f : p.net[0].f
-    OFFGRAD_PICK(W1); OFFGRAD_PICK(b1); OFFGRAD_PICK(W2); OFFGRAD_PICK(b2); OFFGRAD_PICK(W2a); OFFGRAD_PICK(W3); OFFGRAD_PICK(b3);
-    OFFGRAD_PICK(shift); OFFGRAD_PICK(scale); OFFGRAD_PICK(act_scale); OFFGRAD_PICK(n1); OFFGRAD_PICK(n_out);
-    OFFGRAD_PICK(activation); OFFGRAD_PICK(mean_mode);
-#undef OFFGRAD_PICK
+    pick_net(net, blockIdx.y != 0, p.net[0], p.net[1]);
     const bool cat = p.kind == ATACOM_OFFGRAD_TD3;
     const int Q = (int)partial_size(net.n1, 1, p.n_act);
     const NetOffsets o = net_offsets(net.n1, 1);
@@ -546,7 +487,7 @@ __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
         if (live) {
             const double* xr = row_ptr(p.obs, fr, p.n_inner);
             const double* ar = row_ptr(p.action, fr, p.n_inner);
-            for (int e = c; e < p.n_obs; e += 16) me[C::X + e] = (xr[e] - (net.shift ? net.shift[e] : 0.0)) * (net.scale ? net.scale[e] : 1.0);
+            normalise_f64(net, xr, me + C::X, p.n_obs, c);
             if (c < NK) {
                 const double as = c < p.n_act ? ar[c] / (net.act_scale ? net.act_scale[c] : 1.0) : 0.0;
                 me[C::AS + c] = as;
@@ -556,11 +497,9 @@ __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
             if (c == 0) { me[C::ONE] = 1.0; me[C::ZERO] = 0.0; }
         }
         __syncthreads();
-        hidden_f64(net, me, C::X, C::H1, C::H2, p.n_act, live, c);
+        hidden_f64<true>(net, me, C::X, C::H1, C::H2, p.n_act, C::AS, live, c);
         if (live && c == 0) {
-            double q = net.b3[0];
-            for (int j = 0; j < H; ++j) q = __builtin_fma(net.W3[j], me[C::H2 + j], q);
-            const double d = q - p.target[r * p.target_stride];
+            const double d = head_f64(net, me, C::H2, 0) - p.target[r * p.target_stride];
             me[C::DY] = 2.0 * d;
             me[C::ST] = d * d;
         }
@@ -599,18 +538,18 @@ __device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
         double* me = rec + row * C::SIZE;
         if (live) {
             const double* xr = row_ptr(p.obs, fr, p.n_inner);
-            for (int e = c; e < D; e += 16) {
+            for (int e = c; e < D; e += 16) {                    // the header's normalise_f64 for both networks, the row read once
                 me[C::X + e] = (xr[e] - (A.shift ? A.shift[e] : 0.0)) * (A.scale ? A.scale[e] : 1.0);
                 me[C::CX + e] = (xr[e] - (Qn.shift ? Qn.shift[e] : 0.0)) * (Qn.scale ? Qn.scale[e] : 1.0);
             }
             if (c == 0) { me[C::ONE] = 1.0; me[C::ZERO] = 0.0; }
         }
         __syncthreads();
-        hidden_f64(A, me, C::X, C::H1, C::H2, 0, live, c);
+        hidden_f64<true>(A, me, C::X, C::H1, C::H2, 0, C::AS, live, c);
         if (live && c < NK) {
             double a = 0.0, gm = 0.0;
             if (c < k) {
-                double m = A.b3[c];
+                double m = A.b3[c];                              // head_f64, in place: as the call it moves an instruction of this kernel
                 for (int j = 0; j < H; ++j) m = __builtin_fma(A.W3[c * H + j], me[C::H2 + j], m);
                 if (A.mean_mode) {
                     const double s = A.act_scale ? A.act_scale[c] : 1.0, t = ::tanh(m);
@@ -628,12 +567,8 @@ __device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
             if (cat && c < k) me[C::CX + D + c] = as;
         }
         __syncthreads();
-        hidden_f64(Qn, me, C::CX, C::CH1, C::CH2, k, live, c);
-        if (live && c == 0) {
-            double q = Qn.b3[0];
-            for (int j = 0; j < H; ++j) q = __builtin_fma(Qn.W3[j], me[C::CH2 + j], q);
-            me[C::ST] = -q;
-        }
+        hidden_f64<true>(Qn, me, C::CX, C::CH1, C::CH2, k, C::AS, live, c);
+        if (live && c == 0) me[C::ST] = -head_f64(Qn, me, C::CH2, 0);
         __syncthreads();
         if (live)                                                // delta2 of the critic over its h2, in place
             for (int j = c; j < H; j += 16) me[C::CH2 + j] = Qn.W3[j] * act_prime(me[C::CH2 + j], Qn.activation);
@@ -708,11 +643,6 @@ template <typename T>
 Net<T> net_of(const NetDesc& d) {
     return Net<T>{(const T*)d.W1, (const T*)d.b1, (const T*)d.W2, (const T*)d.b2, (const T*)d.W2a, (const T*)d.W3, (const T*)d.b3,
                   (const T*)d.shift, (const T*)d.scale, (const T*)d.act_scale, d.n1, d.n_out, d.activation, d.mean_mode};
-}
-
-template <typename T>
-Rows<T> rows_of(const RowView& v) {
-    return Rows<T>{(const T*)v.ptr, v.so, v.si};
 }
 
 template <typename T>

@@ -1,9 +1,10 @@
 // Launchers of libatacom_soft.so (include/atacom_soft_hip.h): what the C-ABI file calls after it has validated a call, and the
 // sizes both sides agree on.  The kernels are in atacom_soft.hip; nothing here touches the device.  The workgroup and tile
-// constants, tiles() and effective_blocks() are those of ../mlp/atacom_mlp_backward.h.
+// constants, tiles() and effective_blocks() are those of ../mlp/atacom_mlp_backward.h, RowView is that of
+// ../mlp/atacom_mlp_forward.h.
 #pragma once
 #include "../../../include/atacom_soft_hip.h"
-#include "../mlp/atacom_mlp_backward.h"
+#include "../mlp/atacom_mlp_forward.h"
 
 namespace atacom_soft {
 
@@ -20,11 +21,6 @@ __host__ __device__ inline int64_t partial_size(int n_in, int n_out) { return gr
 struct NetDesc {
     const void *W1, *b1, *W2, *b2, *W3, *b3, *shift, *scale;
     int n1, n_out, activation;
-};
-
-struct RowView {
-    const void* ptr;
-    int64_t so, si;
 };
 
 // what the three row kernels share

@@ -8,8 +8,12 @@
 // mlp_forward_mfma, mlp_act16, mlp_act, wave_lds_fence and num<T>.  From ../mlp/atacom_mlp_backward.h (namespace
 // atacom_mlp_backward, shared with the fit, trust and offgrad units), which states the float32 mappings: the row access, layer 1,
 // the transposition buffers, the backward pass from dy on, the accumulators with their hand-over and store, the float64
-// backward loops, column pairs and accumulation, the slice sum of the reduction and the CH switch.  This unit's own: the
-// critics' input gradient, which comes out like the deltas, element 4 g + v of row n16 in register v.
+// backward loops, column pairs and accumulation, the slice sum of the reduction and the CH switch.  From
+// ../mlp/atacom_mlp_forward.h (the same namespace, shared with the offgrad unit), without its WA branch: the block's layout LdsM
+// with AUX, the staging of a network's weights (stage_weights), obs_elem, the float64 layers (normalise_f64, hidden_f64,
+// head_f64), pick_fields and the launchers' RowView / rows_of.  This unit's own: its Net and the AUX words, forward_block, the
+// critics' first-layer input [xn | a], the row arithmetic, and the critics' input gradient, which comes out like the deltas,
+// element 4 g + v of row n16 in register v.
 // LDS: one network block MlpLdsM<4 CH, 64, 8>::NET (act_scale and act_shift in its last 40 floats), 8 floats, and 8 KB of
 // staging per wavefront: 63808 bytes, ONE network resident at a time.  Between the phases a row's values travel in the
 // registers of the lane that owns it (lane l of a wavefront owns row l of its tile).
@@ -139,52 +143,34 @@ __device__ __forceinline__ void actor_row(const Sampled<T>& s, const T (&dq)[NK]
 }
 
 // ------------------------------------------------------------------------------------------------------------ float32
-template <int CH>
-struct LdsM : atacom::MlpLdsM<4 * CH, H, NK> {
-    using L = atacom::MlpLdsM<4 * CH, H, NK>;
-    static constexpr int AUX = L::EXPLORE;             // act_scale [8], act_shift [8]
-};
+// AUX of the block: act_scale [8], act_shift [8]
+template <typename T>
+__device__ __forceinline__ void pick_net(Net<T>& n, bool second, const Net<T>& a, const Net<T>& b) {
+    using N = Net<T>;
+    pick_fields(n, second, a, b, &N::W1, &N::b1, &N::W2, &N::b2, &N::W3, &N::b3, &N::shift, &N::scale, &N::n1, &N::n_out, &N::activation);
+}
 
-// Every word a phase reads is written here, the padding as zero: the W1 slots at or past n1, the W3 rows and biases from n_out
-// to 15.  The observation's normalisation covers the first n_obs elements of the first layer's input.
+// The actor kernels select mu | sigma with the assignments written out: through pick_fields the same selection leaves all
+// sixteen of them other code than they were, k_soft_actor<double>, which fills the register file and spills, 168 bytes longer
+// (profiles/offpolicy_forward_shared.md).  The critic kernels are unchanged through pick_net.
+#define SOFT_PICK_OWN(dst, second, A, B)                                                                                          \
+    dst.W1 = second ? B.W1 : A.W1; dst.b1 = second ? B.b1 : A.b1; dst.W2 = second ? B.W2 : A.W2; dst.b2 = second ? B.b2 : A.b2;     \
+    dst.W3 = second ? B.W3 : A.W3; dst.b3 = second ? B.b3 : A.b3; dst.shift = second ? B.shift : A.shift;                         \
+    dst.scale = second ? B.scale : A.scale; dst.n1 = second ? B.n1 : A.n1; dst.n_out = second ? B.n_out : A.n_out;                 \
+    dst.activation = second ? B.activation : A.activation
+
+// the header's stage_weights (all 16 rows of the W3 block) and this unit's AUX words, between the two barriers of a phase
 template <int CH>
 __device__ __forceinline__ void stage_net(const Net<float>& n, int n_obs, const float* act_scale, const float* act_shift, int n_act, float* lds,
                                           int tid) {
     using L = LdsM<CH>;
     __syncthreads();                                   // the phase before has read its weights
-    // The kernels stage inside their loop over the rounds.  Left visible, the per-thread source addresses of every staging
-    // iteration (they divide by n1) are hoisted out of that loop as 64-bit pairs and spill to scratch; an opaque thread index
-    // keeps them where they are used.
-    asm volatile("" : "+v"(tid));
-    for (int i = tid; i < H * L::S1; i += kBlock) {      // [unit][g][8], slot s of group g = element CH g + s
-        const int u = i / L::S1, g = (i % L::S1) / 8, s = i % 8, e = CH * g + s;
-        lds[L::W1 + i] = (s < CH && e < n.n1) ? n.W1[u * n.n1 + e] : 0.0f;
-    }
-    for (int i = tid; i < H * H; i += kBlock) lds[L::W2 + (i / H) * L::S2 + (i % H)] = n.W2[i];
-    for (int i = tid; i < 16 * H; i += kBlock) lds[L::W3 + (i / H) * L::S2 + (i % H)] = i < n.n_out * H ? n.W3[i] : 0.0f;
-    for (int i = tid; i < H; i += kBlock) { lds[L::B1 + i] = n.b1[i]; lds[L::B2 + i] = n.b2[i]; }
-    for (int i = tid; i < 16; i += kBlock) lds[L::B3 + i] = i < n.n_out ? n.b3[i] : 0.0f;
-    for (int i = tid; i < 32; i += kBlock) {             // [g][8] like W1; past the observation: shift 0, scale 1
-        const int g = i / 8, s = i % 8, e = CH * g + s;
-        const bool real = s < CH && e < n_obs;
-        lds[L::SHIFT + i] = (real && n.shift) ? n.shift[e] : 0.0f;
-        lds[L::SCALE + i] = (real && n.scale) ? n.scale[e] : 1.0f;
-    }
+    stage_weights<CH, false>(n, n_obs, n_act, lds, tid);
     for (int i = tid; i < 8; i += kBlock) {
         lds[L::AUX + i] = (i < n_act && act_scale) ? act_scale[i] : 1.0f;
         lds[L::AUX + 8 + i] = (i < n_act && act_shift) ? act_shift[i] : 0.0f;
     }
     __syncthreads();
-}
-
-// element e of the normalised observation of the row at xr; 0 at or past n_obs.  The load is under the full exec mask.
-template <int CH>
-__device__ __forceinline__ float obs_elem(const float* lds, const float* xr, int e, int n_obs) {
-    using L = LdsM<CH>;
-    const int ec = e < n_obs ? e : n_obs - 1;
-    const int slot = 8 * (ec / CH) + ec % CH;
-    const float v = (xr[ec] - lds[L::SHIFT + slot]) * lds[L::SCALE + slot];
-    return e < n_obs ? v : 0.0f;
 }
 
 // element e of a critic's first-layer input [xn | a], the action's row at ar (memory or LDS); 0 at or past n_obs + n_act
@@ -233,13 +219,6 @@ __device__ __forceinline__ void forward_block(const float* __restrict__ net, con
     o = oa + ob;
 }
 
-// (selected field by field, not indexed: a run-time index into the kernel's argument block would put it in scratch)
-#define SOFT_PICK_NET(dst, second, A, B)                                                                                          \
-    dst.W1 = second ? B.W1 : A.W1; dst.b1 = second ? B.b1 : A.b1; dst.W2 = second ? B.W2 : A.W2; dst.b2 = second ? B.b2 : A.b2;     \
-    dst.W3 = second ? B.W3 : A.W3; dst.b3 = second ? B.b3 : A.b3; dst.shift = second ? B.shift : A.shift;                         \
-    dst.scale = second ? B.scale : A.scale; dst.n1 = second ? B.n1 : A.n1; dst.n_out = second ? B.n_out : A.n_out;                 \
-    dst.activation = second ? B.activation : A.activation
-
 template <int CH>
 __device__ __forceinline__ void critic_f32(const CriticParams<float>& p) {
     constexpr int NT = 4 * CH > 16 ? 2 : 1;
@@ -248,8 +227,7 @@ __device__ __forceinline__ void critic_f32(const CriticParams<float>& p) {
     __shared__ __attribute__((aligned(16))) float lds[kLds];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n16 = lane & 15, g = lane >> 4;
     Net<float> net;
-    const bool second = blockIdx.y != 0;
-    SOFT_PICK_NET(net, second, p.net[0], p.net[1]);
+    pick_net(net, blockIdx.y != 0, p.net[0], p.net[1]);
     stage_net<CH>(net, p.n_obs, nullptr, nullptr, p.n_act, lds, threadIdx.x);
     float* t_act = lds + L::NET + kExtra + wave * kStage;      // activations [16][64]
     float* t_del = t_act + 1024;                                // deltas [16][64]; before them: q [16][8], dy [16][8]
@@ -471,7 +449,7 @@ __device__ __forceinline__ void actor_f32(const ActorParams<float>& p) {
     float* t_del = stage + 1024;
     const bool second = blockIdx.y != 0;                        // this workgroup's network: mu | sigma
     Net<float> own;
-    SOFT_PICK_NET(own, second, p.mu, p.sigma);
+    SOFT_PICK_OWN(own, second, p.mu, p.sigma);
     const float alpha = atacom::num<float>::exp(p.sq.log_alpha[0]);
 
     Grads<NT> acc;
@@ -607,43 +585,13 @@ __device__ __forceinline__ void entry_columns(int e, int n_in, const NetOffsets&
 
 constexpr int kMaxQ = H * 32 + H + H * H + H + H * NK + NK + kStats, kNQ = (kMaxQ + kBlock - 1) / kBlock;
 
-// two hidden layers of a network from the columns cx (n1 values) into the columns ch1, ch2
-__device__ __forceinline__ void hidden_f64(const Net<double>& n, double* me, int cx, int ch1, int ch2, bool live, int c) {
-    if (live)
-        for (int j = c; j < H; j += 16) {
-            double a = n.b1[j];
-            for (int e = 0; e < n.n1; ++e) a = __builtin_fma(n.W1[j * n.n1 + e], me[cx + e], a);
-            me[ch1 + j] = atacom::mlp_act(a, n.activation);
-        }
-    __syncthreads();
-    if (live)
-        for (int j = c; j < H; j += 16) {
-            double a = n.b2[j];
-            for (int i = 0; i < H; ++i) a = __builtin_fma(n.W2[j * H + i], me[ch1 + i], a);
-            me[ch2 + j] = atacom::mlp_act(a, n.activation);
-        }
-    __syncthreads();
-}
-
-// output o of a network from the columns ch2
-__device__ __forceinline__ double head_f64(const Net<double>& n, const double* me, int ch2, int o) {
-    double a = n.b3[o];
-    for (int j = 0; j < H; ++j) a = __builtin_fma(n.W3[o * H + j], me[ch2 + j], a);
-    return a;
-}
-
-__device__ __forceinline__ void normalise_f64(const Net<double>& n, const double* xr, double* dst, int D, int c) {
-    for (int e = c; e < D; e += 16) dst[e] = (xr[e] - (n.shift ? n.shift[e] : 0.0)) * (n.scale ? n.scale[e] : 1.0);
-}
-
 __device__ __forceinline__ void critic_f64(const CriticParams<double>& p) {
     constexpr int R = kRowsF64;
     using C = Rec;
     __shared__ double rec[R * C::SIZE];
     const int tid = threadIdx.x, row = tid >> 4, c = tid & 15;
     Net<double> net;
-    const bool second = blockIdx.y != 0;
-    SOFT_PICK_NET(net, second, p.net[0], p.net[1]);
+    pick_net(net, blockIdx.y != 0, p.net[0], p.net[1]);
     const int Q = (int)partial_size(net.n1, 1);
     const NetOffsets o = net_offsets(net.n1, 1);
     int ca[kNQ], cb[kNQ];
@@ -791,7 +739,7 @@ __device__ __forceinline__ void actor_f64(const ActorParams<double>& p) {
     const int tid = threadIdx.x, row = tid >> 4, c = tid & 15;
     const bool second = blockIdx.y != 0;
     Net<double> own;
-    SOFT_PICK_NET(own, second, p.mu, p.sigma);
+    SOFT_PICK_OWN(own, second, p.mu, p.sigma);
     const double alpha = ::exp(p.sq.log_alpha[0]);
     const int k = p.n_act, D = p.n_obs;
     const int Q = (int)partial_size(D, k);
@@ -934,11 +882,6 @@ template <typename T>
 Net<T> net_of(const NetDesc& d) {
     return Net<T>{(const T*)d.W1, (const T*)d.b1, (const T*)d.W2, (const T*)d.b2, (const T*)d.W3, (const T*)d.b3,
                   (const T*)d.shift, (const T*)d.scale, d.n1, d.n_out, d.activation};
-}
-
-template <typename T>
-Rows<T> rows_of(const RowView& v) {
-    return Rows<T>{(const T*)v.ptr, v.so, v.si};
 }
 
 template <typename T, typename P>

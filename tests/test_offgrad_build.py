@@ -1,7 +1,7 @@
 """CPU-only checks of the 'offgrad' row of build.ADDITIONS, the open table of rl_on_manifold_amd/build.py: the row is there with
 its own properties, build(), stale() and sources() take its key, its include closure is exactly its own files, the borrowed
-headers (the network's LDS layout, the host description, the scaffolding, the view type) and the two headers of csrc/mlp/ (the
-backward pass and the view checks), with nothing of fit, trust, optim or offpolicy, a touched file of its own makes no other
+headers (the network's LDS layout, the host description, the scaffolding, the view type) and the three headers of csrc/mlp/ (the
+forward pass, the backward pass and the view checks), with nothing of fit, trust, optim or offpolicy, a touched file of its own makes no other
 library stale, a touched header of csrc/mlp/ exactly the libraries that share it, its unit is compiled without contraction, and
 the two pinned tables are as they were.  Nothing here counts the rows of ADDITIONS.  No source is edited."""
 import importlib
@@ -12,8 +12,10 @@ import abi_tools as abi
 OWN = {'atacom_offgrad.h', 'atacom_offgrad.hip', 'atacom_offgrad_capi.cpp', 'atacom_offgrad_hip.h'}
 BORROWED = {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h', 'atacom_hip.h',
             'atacom_evaluate_hip.h'}
-# csrc/mlp/: the backward pass it shares with fit, trust and soft; the view checks, which offpolicy includes too
-SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
+# csrc/mlp/: the backward pass it shares with fit, trust and soft; the forward pass in front of it, which it shares with soft;
+# the view checks, which offpolicy includes too
+SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_mlp_forward.h': ['offgrad', 'soft'],
+          'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
 
 
 def test_the_offgrad_row_and_what_follows_from_its_key():

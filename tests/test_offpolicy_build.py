@@ -12,8 +12,10 @@ import abi_tools as abi
 OWN = {'atacom_offpolicy.h', 'atacom_offpolicy.hip', 'atacom_offpolicy_capi.cpp', 'atacom_offpolicy_hip.h'}
 BORROWED = {'atacom_policy.h', 'atacom_quad.h', 'atacom_linalg.h', 'atacom_mlp_host.h', 'atacom_capi_common.h', 'atacom_hip.h',
             'atacom_evaluate_hip.h'}
-# csrc/mlp/: the view checks are in its closure; the backward pass, which fit, trust, offgrad and soft share, is not
-SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
+# csrc/mlp/: the view checks are in its closure; the backward pass, which fit, trust, offgrad and soft share, and the forward
+# pass in front of it, which offgrad and soft share, are not
+SHARED = {'atacom_mlp_backward.h': ['fit', 'trust', 'offgrad', 'soft'], 'atacom_mlp_forward.h': ['offgrad', 'soft'],
+          'atacom_view_checks.h': ['fit', 'trust', 'offpolicy', 'offgrad', 'soft']}
 
 
 def test_the_offpolicy_row_and_what_follows_from_its_key():
@@ -49,7 +51,7 @@ def test_the_include_closure_is_its_own_files_and_the_borrowed_headers():
     assert where['atacom_view_checks.h'] == os.path.join(build.CSRC, 'mlp')
     # nothing of the gradient, trust-region and optimiser libraries nor the backward pass, and it lends nothing
     assert not any(os.path.basename(d) in ('fit', 'trust', 'optim') for d in where.values())
-    assert not any(w in name for name in where for w in ('fit', 'trust', 'optim', 'backward'))
+    assert not any(w in name for name in where for w in ('fit', 'trust', 'optim', 'backward', 'forward'))
     for table in (build.TARGETS, build.EXTENSIONS, build.ADDITIONS):
         for name, t in table.items():
             if name != 'offpolicy':
@@ -74,7 +76,7 @@ def test_a_touched_file_of_its_own_makes_only_offpolicy_stale(monkeypatch):
     touched[:] = ['atacom_evaluate_hip.h']
     assert build.stale('offpolicy')
     for other in ('atacom_fit.hip', 'atacom_fit_hip.h', 'atacom_trust.hip', 'atacom_optim.hip', 'atacom_returns.hip', 'atacom_evaluate.hip',
-                  'atacom_mlp_backward.h'):
+                  'atacom_mlp_backward.h', 'atacom_mlp_forward.h'):
         touched[:] = [other]
         assert not build.stale('offpolicy'), other
     # the shared headers of csrc/mlp/: exactly the libraries named above and nothing else
